@@ -14,15 +14,17 @@ the max-over-ranks of the elapsed time use RCCL.  `--total-images T` switches fr
 
 Legs, in order (all on the launch stream of the engine = torch's current stream):
   1. warm-up (`--warmup` images, untimed) and the TIMED region: exactly `--steps` images, barrier + synchronize on
-     both sides, max over ranks -> `value`, `ms_per_step`; run `--timed-repeats` times (default 2) and the SLOWEST region is the
-     one reported (`timed_regions_seconds` lists them all);
+     both sides, max over ranks -> `value`, `ms_per_step`; run `--timed-repeats` times (default 1; 2 with `--full`) and the SLOWEST
+     region is the one reported (`timed_regions_seconds` lists them all).  `--dump-outputs DIR` then writes what the last timed region
+     returned (`top5`, `final_logits`) as DIR/<name>.npy.  A plain run stops here; legs 2-5 run with `--full` only:
   2. sustained leg: full passes repeated for >= `--sustain-seconds` with a HIP event pair per pass -> mean / p50 / min / max ms
      per image (`sustained`; N=1 runs).  Multi-rank runs: every rank first settles its GPU's clock with untimed passes
      (`--settle-seconds`), the timed region reports each rank's own seconds and the slowest / fastest ratio, and the sustained leg
      runs on EVERY rank concurrently (`distributed.sustained`: per-rank and aggregate images/s);
   3. roofline leg: ONE pass of exactly the pass size the timed region ran, with a HIP event pair round every GEMM and
      attention launch (rlcf_profile_*): dominant-kernel rate, per-shape table of the ViT-B/16 layer kernels (K4-K7);
-  4. cpu_baseline: the oracle (CPU restatement of the reference graph) on BASELINE configs[0] — N=8 views,
+  4. secondary lines of configs[1]: the single-pass f16 mode, checkpoint-grid weights, the drop-in harness loop;
+  5. cpu_baseline: the oracle (CPU restatement of the reference graph) on BASELINE configs[0] — N=8 views,
      selection_p=0.5, C=`--classes` — 1 warm-up + 3 timed samples on the host cores.
 
 `--config {0,1,2,4}` selects the BASELINE.json configuration (default 1 = the one `metric` is quoted on; 3 is config 1 sharded
@@ -31,11 +33,11 @@ over 8 GPUs: `--gpus 8 --total-images 256`):
   1  ViT-B/16 + ViT-B/16, N = 64, prompt tuning                               (rlcf_tta_batch)
   2  ViT-L/14 + ViT-L/14, N = 64, LayerNorm tuning of the image encoder        (rlcf_tta_batch_ln, TPT/tune_cls_rl.py:183-256)
   4  RN50x64 student @448 + ViT-L/14 reward, N = 32, prompt tuning             (one image per pass)
-Every config prints the same JSON shape: whole-step TF/s, F_exec per image, the dominant kernel's roofline and a per-kernel table
+With `--full` every config prints the same JSON shape: whole-step TF/s, F_exec per image, the dominant kernel's roofline and a per-kernel table
 built from ALL profiled launches of one pass (GEMMs by kernel kind and shape incl. the weight-gradient / dX GEMMs, attention forward
 and backward, LayerNorm forward and backward).
 
-Prints ONE JSON line on rank 0.  The numbers a review leans on are repeated as FLAT top-level keys next to `value`
+Prints ONE JSON line on rank 0.  With `--full`, the numbers a review leans on are repeated as FLAT top-level keys next to `value`
 (`value_sustained`, `roofline_frac`, `f16_images_per_s`, `f16_in_proj_frac`, `f16_c_fc_frac`, `f16_attention_frac`,
 `f16_lnfold_*`, `grid_weights_images_per_s`, `harness_one_image_per_call`, `harness_three_in_flight`, ...).
 """
@@ -260,6 +262,24 @@ def harness_leg(dev, student_arch, reward_arch, ssd, rsd, n_cls, n_views, select
     return out
 
 
+def dump_outputs(dirname, arrays, limit_bytes=64 << 20):
+    """`--dump-outputs`: each [rows, ...] array as DIR/<name>.npy in float32 (class indices are exact in float32).  Over `limit_bytes`
+    in all, a fixed seeded sample of the rows, the same for every array, is written instead and its row indices go to rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    per_row = sum(v[0].numel() * 4 for v in arrays.values())
+    if n * per_row > limit_bytes:
+        keep = max(1, (limit_bytes - 8 * n) // per_row)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        np.save(os.path.join(dirname, "rows.npy"), rows.numpy().astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v.numpy())
+    log(f"outputs of the last timed region -> {dirname}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
+
+
 def profile_entries(lib):
     """per-launch records of the roofline leg: (kind, ms, flops, (d0, d1, d2))"""
     out = []
@@ -309,8 +329,9 @@ def main():
     ap.add_argument("--total-images", type=int, default=0,
                     help="strong scaling: this many test images in total, split over the ranks (BASELINE configs[3]: 256); overrides --steps")
     ap.add_argument("--sustain-seconds", type=float, default=3.0, help="length of the sustained leg (0 = skip)")
-    ap.add_argument("--timed-repeats", type=int, default=2,
-                    help="how many times the timed region (exactly --steps images, barrier + synchronize on both sides) is run; the slowest is `value`")
+    ap.add_argument("--timed-repeats", type=int, default=None,
+                    help="how many times the timed region (exactly --steps images, barrier + synchronize on both sides) is run; the slowest is "
+                         "`value` (default: 1; 2 with --full)")
     ap.add_argument("--settle-seconds", type=float, default=1.0,
                     help="multi-rank runs: untimed passes of the timed pass size for this long before the barrier (clock / power settle)")
     ap.add_argument("--weights", default="fp32", choices=["fp32", "fp16grid"],
@@ -323,6 +344,11 @@ def main():
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-launch profiling leg (rocprofv3 runs: fewer launches in the trace)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real multi-GPU runs; gloo lets two ranks share one GPU in a smoke test")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: a second timed region, the roofline, sustained, secondary f16 / grid-weights, "
+                         "harness and CPU-baseline legs (each --no-* / --sustain-seconds switch above still applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed region computed (rank 0: top5, final_logits) as DIR/<name>.npy, float32, at most 64 MB")
     a = ap.parse_args()
     # `python bench.py --gpus N` typed without a launcher: become N ranks under torch.distributed.run (rlcf_amd/shard.py)
     rc = shard.self_launch(a.gpus, sys.argv[1:])
@@ -333,6 +359,7 @@ def main():
     if a.warmup is None: a.warmup = wl.get("warmup", 32)
     a.views = a.views if a.views is not None else wl["views"]
     if a.tta_steps is None: a.tta_steps = wl.get("tta_steps", 1)
+    if a.timed_repeats is None: a.timed_repeats = 2 if a.full else 1
     a.reward_arch = a.reward_arch or wl["reward"]
     student_arch, mode_ln = wl["student"], wl["mode"] == "ln"
     is_default_wl = (a.views, a.reward_arch, a.classes, a.tta_steps) == (wl["views"], wl["reward"], 1000, wl.get("tta_steps", 1))
@@ -388,7 +415,7 @@ def main():
     eng.set_class_bank(tokens, n_ctx, ctx0, mode)
     log("engine ready")
     cfg = TTAConfig(selection_p=wl["selection_p"], tta_steps=a.tta_steps, sample_k=3, lr=wl["lr"], weight_decay=5e-4)
-    run_pass = (lambda v: eng.tta_batch_ln(v, cfg)) if mode_ln else (lambda v: eng.tta_batch(v, cfg))
+    run_pass = (lambda v: eng.tta_batch_ln(v, cfg, want_logits=True)) if mode_ln else (lambda v: eng.tta_batch(v, cfg, want_logits=True))
 
     # which test images this rank times: weak scaling = `steps` images of its own; strong = its shard of a fixed stream
     if a.total_images > 0:
@@ -430,7 +457,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        top5 = run_pass(views)
+        top5, final_logits = run_pass(views)
         torch.cuda.synchronize()
         own_ = time.perf_counter() - t0                  # this rank's own K steps (before it waits for the others)
         if use_dist:
@@ -455,8 +482,11 @@ def main():
     log(f"timed region: {total_steps} images in {dt:.3f} s")
     ms_per_step = dt / (total_steps / world) * 1e3       # per rank: every rank runs total/world images concurrently
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"top5": top5, "final_logits": final_logits})
+
     dist_sustained = None
-    if use_dist and a.sustain_seconds > 0:
+    if use_dist and a.full and a.sustain_seconds > 0:
         # ---- sustained leg of a multi-rank run: EVERY rank repeats full passes for >= sustain_seconds at the same time (barrier in
         # front, none inside), one HIP event pair per pass; the per-rank rates are gathered (the aggregate is their sum: no rank waits
         # for another on the data path)
@@ -511,7 +541,7 @@ def main():
         }
         if dist_info:
             out["distributed"] = dist_info
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             # ---- roofline leg: one pass of exactly the timed pass size, HIP event pair per GEMM / attention / LayerNorm launch
             lib.rlcf_profile_gemm(1)
             run_pass(views[:pass_images])
@@ -604,7 +634,7 @@ def main():
                 # the profiled pass is the timed pass: its GEMM time cannot exceed the step time (5 % for event overhead / clock drift)
                 "check_gemm_time_within_step": bool(g_ms / pass_images <= 1.05 * ms_per_step),
             }
-        if world == 1 and a.sustain_seconds > 0 and not use_dist:
+        if a.full and world == 1 and a.sustain_seconds > 0 and not use_dist:
             # ---- sustained leg: full passes for >= sustain_seconds, a HIP event pair per pass (p50 / mean)
             pv = views[:pass_images]
             # shader clock / socket power while the passes run (rocm-smi at ~3 Hz from a host thread): under this load the package sits
@@ -657,7 +687,7 @@ def main():
                     out["roofline"]["peak_at_sustained_clock"] = out["roofline"]["peak"] * sclk / 2400.0
                     out["roofline"]["frac_at_sustained_clock"] = out["roofline"]["achieved"] / out["roofline"]["peak_at_sustained_clock"]
                     out["roofline"]["frac_of_mfma_pipe_at_sustained_clock"] = out["roofline"]["frac_of_mfma_pipe"] * 2400.0 / sclk
-        if world == 1 and a.precision == "f16x3" and a.config == 1 and not a.no_f16_line and not use_dist:
+        if a.full and world == 1 and a.precision == "f16x3" and a.config == 1 and not a.no_f16_line and not use_dist:
             # ---- secondary, clearly labelled: the reference's own GPU arithmetic (fp16 autocast, tpt_cls_rl.py:52) = RLCF_PREC_F16.
             # Not the headline and not parity-grade: reported with its measured deviation from the split-f16 engine on this very pass.
             # Two forms: the DEFAULT (f32 residual stream: keeps the reference's top-1 on 32 / 32 stream samples) and the opt-in with the
@@ -718,7 +748,7 @@ def main():
                 notes="profiles/r6_notes.md")
             eh.close()
             log("secondary f16 line done")
-        if world == 1 and a.precision == "f16x3" and a.config == 1 and not a.no_f16_line and not use_dist and a.weights == "fp32":
+        if a.full and world == 1 and a.precision == "f16x3" and a.config == 1 and not a.no_f16_line and not use_dist and a.weights == "fp32":
             # ---- secondary, parity-grade: the same step with the GEMM weights on the fp16 GRID, as every released CLIP checkpoint has them
             # (the archives the reference loads store Conv / Linear / attention / projection weights as fp16; TPT/clip/model.py:375-436
             # copies them into float32 parameters).  Their split-f16 lo halves are zero, the engine finds that out at finalize and the
@@ -759,7 +789,7 @@ def main():
                 "dominant_gemm_frac_of_mfma_pipe": 2.0 * ach_g / PEAK_TFLOPS["f16"]}
             eg.close()
             log("secondary fp16-grid-weights line done")
-        if world == 1 and a.config == 1 and is_default_wl and a.precision == "f16x3" and not a.no_harness_leg and not use_dist:
+        if a.full and world == 1 and a.config == 1 and is_default_wl and a.precision == "f16x3" and not a.no_harness_leg and not use_dist:
             eng.close()                                      # (the mirror builds its own engine: free this one's workspace first)
             eng = None
             out["harness"] = harness_leg(dev, student_arch, a.reward_arch, ssd, rsd, a.classes, a.views, wl["selection_p"], wl["lr"])
@@ -770,7 +800,7 @@ def main():
                 hg["what"] = "the harness leg above with the GEMM weights on the fp16 grid (as a released checkpoint holds them): one image per pass"
                 out["harness_checkpoint_grid_weights"] = hg
             log("harness leg done")
-        if world == 1 and not a.no_cpu_baseline and not use_dist:
+        if a.full and world == 1 and not a.no_cpu_baseline and not use_dist:
             # the reference's CPU path runs BASELINE configs[0] (ViT-B/16, N = 8): timed for configs 0 / 1; the ViT-L/14 and RN50x64
             # configurations would take minutes per image on the host and get the same oracle leg only when asked for with a budget
             if a.config in (0, 1):
@@ -778,39 +808,40 @@ def main():
                                                    budget_s=a.cpu_baseline_budget)
             # (configs 2 / 4: no `cpu_baseline` key — the oracle's CPU leg is BASELINE configs[0]; a ViT-L/14 or RN50x64 sample takes the
             # host minutes, and a null would read as a measurement)
-        # ---- flat copies of the numbers a review leans on, next to `value` (the driver's parsed record keeps top-level scalars)
-        def _g(d, *ks):
-            for k in ks:
-                d = d.get(k) if isinstance(d, dict) else None
-                if d is None:
-                    return None
-            return d
-        out["value_sustained"] = _g(out, "sustained", "images_per_s_mean")
-        out["roofline_frac"] = _g(out, "roofline", "frac")
-        for row in _g(out, "roofline", "per_kernel") or []:
-            if row["kernel"].startswith("K5"):
-                out["attention_fwd_frac_of_hbm_roofline"] = row.get("frac_of_hbm_roofline")
-        for k_flat, ks in (("f16_images_per_s", ("secondary_f16_single_pass", "images_per_s")),
-                           ("f16_in_proj_frac", ("secondary_f16_single_pass", "in_proj_qkv_gemm_frac_of_f16_peak")),
-                           ("f16_c_fc_frac", ("secondary_f16_single_pass", "c_fc_gemm_frac_of_f16_peak")),
-                           ("f16_c_proj_frac", ("secondary_f16_single_pass", "c_proj_gemm_frac_of_f16_peak")),
-                           ("f16_out_proj_frac", ("secondary_f16_single_pass", "out_proj_gemm_frac_of_f16_peak")),
-                           ("f16_attention_frac", ("secondary_f16_single_pass", "attention_fwd_frac_of_f16_peak")),
-                           ("f16_attention_frac_of_hbm_roofline", ("secondary_f16_single_pass", "attention_fwd_frac_of_hbm_roofline")),
-                           ("f16_top1_agreement", ("secondary_f16_single_pass", "top1_agreement_vs_split_f16")),
-                           ("f16_lnfold_images_per_s", ("secondary_f16_single_pass", "lnfold_opt_in", "images_per_s")),
-                           ("f16_lnfold_in_proj_frac", ("secondary_f16_single_pass", "lnfold_opt_in", "in_proj_qkv_gemm_frac_of_f16_peak")),
-                           ("f16_lnfold_c_fc_frac", ("secondary_f16_single_pass", "lnfold_opt_in", "c_fc_gemm_frac_of_f16_peak")),
-                           ("grid_weights_images_per_s", ("secondary_checkpoint_grid_weights", "images_per_s")),
-                           ("harness_one_image_per_call", ("harness", "images_per_s_one_image_per_pass_staged_views")),
-                           ("harness_one_image_per_call_views_in_loop", ("harness", "images_per_s_one_image_per_pass_views_in_loop")),
-                           ("harness_three_in_flight", ("harness", "images_per_s_one_image_per_pass_three_in_flight_staged_views")),
-                           ("harness_three_in_flight_views_in_loop", ("harness", "images_per_s_one_image_per_pass_three_in_flight_views_in_loop")),
-                           ("harness_three_in_flight_legs_spread", ("harness", "three_in_flight_staged_legs_max_over_min")),
-                           ("harness_three_in_flight_views_in_loop_legs_spread", ("harness", "three_in_flight_views_in_loop_legs_max_over_min")),
-                           ("view_generation_ms_per_image", ("harness", "view_generation_ms_per_image")),
-                           ("cpu_baseline_images_per_s", ("cpu_baseline", "value"))):
-            out[k_flat] = _g(out, *ks)
+        if a.full:
+            # ---- flat copies of the numbers a review leans on, next to `value` (the driver's parsed record keeps top-level scalars)
+            def _g(d, *ks):
+                for k in ks:
+                    d = d.get(k) if isinstance(d, dict) else None
+                    if d is None:
+                        return None
+                return d
+            out["value_sustained"] = _g(out, "sustained", "images_per_s_mean")
+            out["roofline_frac"] = _g(out, "roofline", "frac")
+            for row in _g(out, "roofline", "per_kernel") or []:
+                if row["kernel"].startswith("K5"):
+                    out["attention_fwd_frac_of_hbm_roofline"] = row.get("frac_of_hbm_roofline")
+            for k_flat, ks in (("f16_images_per_s", ("secondary_f16_single_pass", "images_per_s")),
+                               ("f16_in_proj_frac", ("secondary_f16_single_pass", "in_proj_qkv_gemm_frac_of_f16_peak")),
+                               ("f16_c_fc_frac", ("secondary_f16_single_pass", "c_fc_gemm_frac_of_f16_peak")),
+                               ("f16_c_proj_frac", ("secondary_f16_single_pass", "c_proj_gemm_frac_of_f16_peak")),
+                               ("f16_out_proj_frac", ("secondary_f16_single_pass", "out_proj_gemm_frac_of_f16_peak")),
+                               ("f16_attention_frac", ("secondary_f16_single_pass", "attention_fwd_frac_of_f16_peak")),
+                               ("f16_attention_frac_of_hbm_roofline", ("secondary_f16_single_pass", "attention_fwd_frac_of_hbm_roofline")),
+                               ("f16_top1_agreement", ("secondary_f16_single_pass", "top1_agreement_vs_split_f16")),
+                               ("f16_lnfold_images_per_s", ("secondary_f16_single_pass", "lnfold_opt_in", "images_per_s")),
+                               ("f16_lnfold_in_proj_frac", ("secondary_f16_single_pass", "lnfold_opt_in", "in_proj_qkv_gemm_frac_of_f16_peak")),
+                               ("f16_lnfold_c_fc_frac", ("secondary_f16_single_pass", "lnfold_opt_in", "c_fc_gemm_frac_of_f16_peak")),
+                               ("grid_weights_images_per_s", ("secondary_checkpoint_grid_weights", "images_per_s")),
+                               ("harness_one_image_per_call", ("harness", "images_per_s_one_image_per_pass_staged_views")),
+                               ("harness_one_image_per_call_views_in_loop", ("harness", "images_per_s_one_image_per_pass_views_in_loop")),
+                               ("harness_three_in_flight", ("harness", "images_per_s_one_image_per_pass_three_in_flight_staged_views")),
+                               ("harness_three_in_flight_views_in_loop", ("harness", "images_per_s_one_image_per_pass_three_in_flight_views_in_loop")),
+                               ("harness_three_in_flight_legs_spread", ("harness", "three_in_flight_staged_legs_max_over_min")),
+                               ("harness_three_in_flight_views_in_loop_legs_spread", ("harness", "three_in_flight_views_in_loop_legs_max_over_min")),
+                               ("view_generation_ms_per_image", ("harness", "view_generation_ms_per_image")),
+                               ("cpu_baseline_images_per_s", ("cpu_baseline", "value"))):
+                out[k_flat] = _g(out, *ks)
         print(json.dumps(out))
     if eng is not None:
         eng.close()

@@ -160,7 +160,8 @@ SIGNATURES = {
 
 def build(verbose: bool = False) -> str:
     """Compile librlcf_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
-    r = subprocess.run(["make", "-C", CSRC, "-j", str(os.cpu_count() or 4)], capture_output=True, text=True)
+    jobs = int(os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16))     # (a shared build host may show far more cores than it grants)
+    r = subprocess.run(["make", "-C", CSRC, "-j", str(jobs)], capture_output=True, text=True)
     if verbose or r.returncode != 0:
         print(r.stdout[-4000:], r.stderr[-4000:])
     if r.returncode != 0 or not os.path.exists(LIB_PATH):

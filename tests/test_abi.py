@@ -51,18 +51,24 @@ def test_struct_layouts(lib):
     assert C.sizeof(lib.Crop) == 20 and C.sizeof(lib.AugmixOp) == 56          # rlcf_crop, rlcf_augmix_op {int, int, double[6]}
 
 
-def test_bpe_tokenizer_matches_reference_fixture():
-    """rlcf_amd.bpe.ClipBPE vs clip.tokenize of the reference (tests/golden/tokenizer.npz).  Needs OpenAI's merges file,
-    which is data this repo does not ship: read from the reference checkout when present."""
+def test_bpe_tokenizer_matches_reference_fixture(tmp_path):
+    """rlcf_amd.bpe.ClipBPE vs clip.tokenize of the reference (tests/golden/tokenizer.npz).  OpenAI's merges file is data this repo
+    does not ship: the merges these strings use keep their ranks (tests/golden/bpe_merges_used.npz, make_bpe_golden.py) in a file of
+    the full length whose other ranks hold merges that never match, so every id is the one the full vocabulary gives."""
+    import gzip
     import sys
     import numpy as np
-    vocab = os.environ.get("RLCF_BPE_VOCAB", "/root/reference/TPT/clip/bpe_simple_vocab_16e6.txt.gz")
-    if not os.path.exists(vocab):
-        pytest.skip("BPE merges file not available")
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     from make_golden import TOKENIZER_STRINGS
-    from rlcf_amd.bpe import ClipBPE
-    tok = ClipBPE(vocab)
+    from rlcf_amd.bpe import N_MERGES, ClipBPE
+    used = np.load(os.path.join(ROOT, "tests", "golden", "bpe_merges_used.npz"))
+    lines = [f"\ue000{r} \ue001" for r in range(N_MERGES)]     # (private-use characters: no byte of any text maps to them)
+    for r, (a, b) in zip(used["ranks"].tolist(), used["merges"].tolist()):
+        lines[r] = f"{a} {b}"
+    vocab = tmp_path / "bpe_merges.txt.gz"
+    with gzip.open(vocab, "wt", encoding="utf-8") as f:
+        f.write("#version: 0.2\n" + "\n".join(lines) + "\n")
+    tok = ClipBPE(str(vocab))
     got = tok.tokenize(TOKENIZER_STRINGS).numpy()
     ref = np.load(os.path.join(ROOT, "tests", "golden", "tokenizer.npz"))["tokens"]
     assert got.shape == ref.shape and (got == ref).all()

@@ -305,7 +305,7 @@ def test_bench_strong_scaling_line_two_ranks(L, dev):
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29519", "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--total-images", "6", "--warmup", "2",
-                        "--views", "16", "--classes", "64", "--batch", "2", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True,
+                        "--views", "16", "--classes", "64", "--batch", "2", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -320,7 +320,7 @@ def test_bench_runs_the_rccl_path_with_one_rank(L, dev):
     init_process_group("nccl", device_id=...), both barriers and the CUDA-tensor all_reduce(MAX) of the elapsed time execute; the line
     reports the rank count RCCL saw and is otherwise the line of the plain single-process run (same first prediction, same executed
     FLOPs, same configuration)."""
-    small = ["--steps", "4", "--warmup", "2", "--batch", "2", "--classes", "50", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-f16-line"]
+    small = ["--steps", "4", "--warmup", "2", "--batch", "2", "--classes", "50", "--no-cpu-baseline", "--sustain-seconds", "0", "--no-f16-line", "--full"]
     plain = _run_json([sys.executable, "bench.py"] + small)
     rccl = _run_json(_torchrun(29541) + ["bench.py", "--gpus", "1", "--dist-backend", "nccl"] + small, env={"RLCF_FORCE_DIST": "1"})
     assert rccl["distributed"]["rccl_ranks"] == 1 and "RCCL" in rccl["distributed"]["backend"]
@@ -329,6 +329,25 @@ def test_bench_runs_the_rccl_path_with_one_rank(L, dev):
         assert rccl[k] == plain[k], k
     assert abs(rccl["flops_exec_per_image"] - plain["flops_exec_per_image"]) <= 1e-6 * plain["flops_exec_per_image"]
     assert rccl["value"] > 0 and rccl["roofline"]["frac"] > 0
+
+
+def test_bench_plain_line_times_steps_and_dumps_the_same_outputs(L, dev, tmp_path):
+    """A plain `bench.py` (no --full) times exactly --steps images once and runs no other leg; --dump-outputs writes what that timed
+    region returned, and two runs with the same arguments write the same arrays (seeded inputs, episodic steps)."""
+    import numpy as np
+    args = ["--steps", "4", "--warmup", "2", "--batch", "2", "--classes", "50"]
+    runs = [_run_json([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for rec in runs:
+        assert rec["steps"] == 4 and len(rec["timed_regions_seconds"]) == 1
+        assert abs(rec["ms_per_step"] * 4 - rec["timed_regions_seconds"][0] * 1e3) < 1e-6 * rec["ms_per_step"] * 4
+        assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+        assert not {"roofline", "sustained", "cpu_baseline", "harness", "value_sustained"} & set(rec)
+    for name, shape in (("top5", (4, 5)), ("final_logits", (4, 50))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.shape == shape and a.dtype == np.float32 and np.array_equal(a, b), name
+    top5 = np.load(tmp_path / "a" / "top5.npy")
+    assert top5[0, 0] == runs[0]["top1_first"]
+    assert (np.argmax(np.load(tmp_path / "a" / "final_logits.npy"), axis=1) == top5[:, 0]).all()
 
 
 def test_eval_driver_runs_the_rccl_path_with_one_rank(L, dev):
@@ -382,7 +401,7 @@ def test_bench_config_switch_emits_the_contract_line(L, dev, config, classes):
     tower) emit the same JSON shape as the headline config: metric / value / roofline with a per-kernel table that names backward
     kernels where the configuration has them."""
     line = _run_json([sys.executable, "bench.py", "--config", str(config), "--steps", "2", "--warmup", "1", "--classes", str(classes),
-                      "--no-cpu-baseline", "--sustain-seconds", "0"])
+                      "--no-cpu-baseline", "--sustain-seconds", "0", "--full"])
     assert line["metric"] and line["unit"] == "images/s" and line["value"] > 0 and line["n_gpus"] == 1 and line["steps"] == 2
     assert line["higher_is_better"] is True and line["config"]["classes"] == classes
     arch = {0: "ViT-B/16 student", 2: "ViT-L/14 student", 4: "RN50x64 student"}[config]

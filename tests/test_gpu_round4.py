@@ -62,7 +62,7 @@ def test_bench_multi_rank_timing_record():
     slowest / fastest ratio, the settle passes, and a sustained leg that ran on EVERY rank."""
     r = subprocess.run(_torchrun(2, 29529) + ["bench.py", "--gpus", "2", "--dist-backend", "gloo", "--steps", "4", "--warmup", "2", "--views", "16",
                                               "--classes", "64", "--batch", "2", "--no-cpu-baseline", "--sustain-seconds", "0.5",
-                                              "--settle-seconds", "0.3"], cwd=ROOT, env=ENV, capture_output=True, text=True, timeout=900)
+                                              "--settle-seconds", "0.3", "--full"], cwd=ROOT, env=ENV, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     d = rec["distributed"]

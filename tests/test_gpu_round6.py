@@ -188,7 +188,7 @@ def test_bench_two_ranks_rccl_preflight():
     first time RCCL sees more than one rank on this code is inside the GPU suite of the first multi-GPU box, not in the driver's
     scaling run."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "nccl", "--steps", "8", "--warmup", "4",
-                        "--no-cpu-baseline", "--sustain-seconds", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-cpu-baseline", "--sustain-seconds", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["distributed"]["rccl_ranks"] == 2 and line["value"] > 0

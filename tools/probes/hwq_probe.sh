@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r6
 for Q in 4 8 4 8; do
   echo "== GPU_MAX_HW_QUEUES=$Q"
-  GPU_MAX_HW_QUEUES=$Q timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f16-line --no-roofline --sustain-seconds 0 --timed-repeats 1 2>/dev/null | python -c "
+  GPU_MAX_HW_QUEUES=$Q timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f16-line --no-roofline --sustain-seconds 0 --timed-repeats 1 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

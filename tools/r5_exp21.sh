@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r5/exp21; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_round5.py -x -q -m gpu -k "in_flight or conveniences" > $O/pytest.txt 2>&1; tail -8 $O/pytest.txt
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --no-f16-line > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --no-f16-line > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r5/exp21/bench.json").read().strip().splitlines()[-1])

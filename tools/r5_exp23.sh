@@ -3,7 +3,7 @@ set -u
 O=gpurun_out/r5/exp23; mkdir -p $O
 for q in 8 16; do
 echo "GPU_MAX_HW_QUEUES=$q"
-GPU_MAX_HW_QUEUES=$q timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --no-f16-line > $O/bench$q.json 2> $O/bench$q.err
+GPU_MAX_HW_QUEUES=$q timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --no-f16-line > $O/bench$q.json 2> $O/bench$q.err
 python - $q <<'PY'
 import json, sys
 d = json.loads(open(f"gpurun_out/r5/exp23/bench{sys.argv[1]}.json").read().strip().splitlines()[-1])

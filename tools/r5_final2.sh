@@ -4,9 +4,9 @@
 set -u
 O=gpurun_out/r5/final4; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -5 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench.err; python -c "
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench.err; python -c "
 import json; d=json.loads(open('$O/bench_driver_cmdline.json').read().strip().splitlines()[-1]); print('headline', d['value'], 'grid', d['secondary_checkpoint_grid_weights']['images_per_s'], 'f16', d['secondary_f16_single_pass']['images_per_s'], {k:round(v,1) for k,v in d['harness'].items() if isinstance(v,float)})"
-run() { name=$1; shift; timeout 900 python bench.py "$@" --weights fp16grid --no-cpu-baseline > $O/$name.json 2> $O/$name.err; python -c "
+run() { name=$1; shift; timeout 900 python bench.py --full "$@" --weights fp16grid --no-cpu-baseline > $O/$name.json 2> $O/$name.err; python -c "
 import json; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); r=d.get('roofline') or {}; print('$name', round(d['value'],2), 'ms', round(d['ms_per_step'],3), 'dom TF', round(r.get('achieved',0),1), 'harness', {k:round(v,1) for k,v in (d.get('harness') or {}).items() if isinstance(v,float)})" || tail -3 $O/$name.err; }
 run grid_driver --steps 20 --warmup 5
 run grid_default

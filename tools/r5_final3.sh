@@ -4,8 +4,8 @@ set -u
 O=gpurun_out/r5/final3; mkdir -p $O
 timeout 2400 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench_driver_cmdline.err
-timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench_driver_cmdline.err
+timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 for n in ("bench_driver_cmdline", "bench_default"):

@@ -3,7 +3,7 @@
 # (parity mode and the f16 mode), fabric traffic + SQ counters of the dominant GEMM, the GPU suite in BOTH stream modes; -> gpurun_out/r6/final
 set -u
 O=gpurun_out/r6/final; mkdir -p $O
-run() { name=$1; shift; timeout 900 python bench.py "$@" > $O/$name.json 2> $O/$name.err; echo "$name rc=$?"; }
+run() { name=$1; shift; timeout 900 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err; echo "$name rc=$?"; }
 run bench_driver_cmdline --steps 20 --warmup 5
 run bench_default --no-cpu-baseline
 run bench_c0 --config 0 --no-cpu-baseline
@@ -12,13 +12,13 @@ run bench_c4 --config 4 --no-cpu-baseline
 run bench_c5 --config 5 --no-cpu-baseline
 run bench_batch1 --batch 1 --no-cpu-baseline
 export TMPDIR=/tmp
-prof() { name=$1; nimg=$2; title=$3; shift 3; timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -- python bench.py "$@" > $O/prof_$name.log 2>&1
+prof() { name=$1; nimg=$2; title=$3; shift 3; timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -- python bench.py --full "$@" > $O/prof_$name.log 2>&1
          db=$(find /tmp/prof_$name -name "*_results.db" | head -1)
          if [ -n "$db" ]; then python tools/prof_summary.py "$db" "$title" $nimg > $O/kernel_stats_$name.txt; else echo "prof $name: no database"; fi
          tail -c 1500 $O/prof_$name.log > $O/prof_$name.tail; rm -f $O/prof_$name.log; rm -rf /tmp/prof_$name; }
 C="--no-cpu-baseline --sustain-seconds 0 --no-f16-line --no-harness-leg"
-prof c1 85 "round 6 final build: rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 $C (BASELINE configs[1]; set-up pass of 20 + 5 warm-up + 2 x 20 timed + 20 profiled images = 85)" --steps 20 --warmup 5 $C
-prof f16 85 "round 6 final build: rocprofv3 --kernel-trace --stats -- python bench.py --precision f16 --steps 20 --warmup 5 $C (RLCF_PREC_F16 default form, NOT parity-grade; 85 images)" --precision f16 --steps 20 --warmup 5 $C
+prof c1 85 "round 6 final build: rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 $C (BASELINE configs[1]; set-up pass of 20 + 5 warm-up + 2 x 20 timed + 20 profiled images = 85)" --steps 20 --warmup 5 $C
+prof f16 85 "round 6 final build: rocprofv3 --kernel-trace --stats -- python bench.py --full --precision f16 --steps 20 --warmup 5 $C (RLCF_PREC_F16 default form, NOT parity-grade; 85 images)" --precision f16 --steps 20 --warmup 5 $C
 # fabric traffic of the dominant GEMM (separate --pmc passes), M = 252 160 (20 images per pass) and 403 456 (32)
 R=$PWD
 for M in 252160 403456; do

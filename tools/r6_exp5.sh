@@ -4,7 +4,7 @@
 O=gpurun_out/r6; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_round2.py -q -m gpu -x 2>&1 | tail -3 > $O/exp5_linest.txt
 for r in 1 2 3; do for T in 0 1; do
-  echo "== round $r LINEST=$T"; RLCF_X3_LINEST=$T timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-harness-leg --no-f16-line --no-roofline --timed-repeats 1 --sustain-seconds 0 2>&1 | python -c "
+  echo "== round $r LINEST=$T"; RLCF_X3_LINEST=$T timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-harness-leg --no-f16-line --no-roofline --timed-repeats 1 --sustain-seconds 0 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 # with the ablation library; the GPU suite on the NULL stream
 set -u
 O=gpurun_out/r6; mkdir -p $O
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench_driver_cmdline.err; echo "bench rc=$?"; tail -3 $O/bench_driver_cmdline.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_cmdline.json 2> $O/bench_driver_cmdline.err; echo "bench rc=$?"; tail -3 $O/bench_driver_cmdline.err
 python - <<'PY'
 import json
 try:
