@@ -79,13 +79,17 @@ typedef struct { int q_start, q_len, pre_start, pre_len; } rlcf_seq;
 
 /* C[M,N] = epi(alpha * A[M,K] . W[N,K]^T + bias[N]) (+ residual[M,N]).  Replaces the
  * nn.Linear / in_proj / out_proj / `@ proj` call sites TPT/clip/model.py:175-191,235-238,
- * custom_clip.py:71,332-333.  K % 16 == 0.  bias/residual/aux may be NULL. */
+ * custom_clip.py:71,332-333.  K % 16 == 0.  bias/residual/aux may be NULL.
+ * precision RLCF_PREC_F16X3 (an op-level convenience, not the engine's path): both operands are split into f16 pairs with their own
+ * power-of-two pre-scale (max|x| lifted into [2^9, 2^10), undone in alpha), so operands of any finite range are accepted; max|A| and
+ * max|W| are read back to the host first, so this form synchronises the stream and cannot be captured into a graph.  An infinite
+ * operand is refused (RLCF_ERR_ARG); a NaN propagates into the outputs it touches, as in RLCF_PREC_F32. */
 int rlcf_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias,
                  const float* residual, int ldr, const float* aux, int ldaux,
                  float* C, int ldc, int M, int N, int K, float alpha, int epilogue, int precision,
                  rlcf_stream stream);
 
-/* Split-f16 operand pairs (RLCF_PREC_F16X3): x = hi + lo with hi = f16(x), lo = f16(x-hi) (operands should be O(1):
+/* Split-f16 operand pairs (RLCF_PREC_F16X3): x = hi + lo with hi = f16(x), lo = f16(x-hi) (operands of these two calls should be O(1):
  * below |x| = 2^-3 the absolute error floor is 2^-25; the engine pre-scales weights and gradients by exact powers of two);
  * n % 8 == 0.  rlcf_gemm_f16x3 is rlcf_gemm_nt on pre-split operands (3 f16 MFMAs per product,
  * f32 accumulate); output f32 (C) and/or a split pair (Chi, Clo).  K % 32 == 0. */
@@ -111,7 +115,11 @@ int rlcf_gemm_f16(const void* A, int lda, const void* W, int ldw, const float* b
  *   mode 2 (out_proj, c_proj + residual add): out16[M,N] (the residual stream, IN PLACE) = f16(out16 + alpha A.W^T + bias), and the partial
  *          (sum, sum of squares) of every updated row over each 64-column slice goes to ln_part [(N/64)][M][2];
  * rlcf_ln_stats_final adds the N/64 partials of a row in order -> ln_mr (eps 1e-5, biased variance: nn.LayerNorm);  rlcf_resid16_init
- * rounds an f32 stream to f16 rows and leaves their (mean, rstd).  N % 256 == 0, K % 128 == 0, K >= 256. */
+ * rounds an f32 stream to f16 rows and leaves their (mean, rstd).  N % 256 == 0, K % 128 == 0, K >= 256.
+ * The row statistics (rlcf_resid16_init, and mode 2's partials through rlcf_ln_stats_final) come from one-pass (sum, sum of squares) in
+ * f32: the variance loses ~(mean / std)^2 2^-24 of itself, so they hold for rows with |mean| / std up to ~8 (trained towers' residual
+ * rows stay below 0.25: tests/test_trained_profile.py) and are NOT accurate for rows with a large common offset (mean 1e3, std 0.1).
+ * tests/test_gpu_dynamic_range.py pins that range for both forms. */
 int rlcf_gemm_f16_ln(const void* A, int lda, const void* W, int ldw, const float* bias, void* out16, int ldo, int M, int N, int K, float alpha,
                      int epilogue, int mode, const float* ln_mr, const float* ln_s, float* ln_part, rlcf_stream stream);
 int rlcf_ln_stats_final(const float* ln_part, int parts, int rows, int width, float* ln_mr, rlcf_stream stream);

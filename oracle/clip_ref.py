@@ -25,8 +25,9 @@ LN_EPS = 1e-5          # nn.LayerNorm default, used by TPT/clip/model.py:157-163
 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """TPT/clip/model.py:157-163 — LayerNorm evaluated in fp32, biased variance."""
-    x = x.float()
+    """TPT/clip/model.py:157-163 — LayerNorm evaluated in fp32, biased variance (float64 inputs stay float64: the high-precision
+    checker of the trained-profile tests)."""
+    x = x if x.dtype == torch.float64 else x.float()
     mu = x.mean(dim=-1, keepdim=True)
     var = ((x - mu) ** 2).mean(dim=-1, keepdim=True)
     return (x - mu) * torch.rsqrt(var + LN_EPS) * w + b
@@ -188,7 +189,7 @@ def encode_image(sd: SD, images: torch.Tensor) -> torch.Tensor:
     w = sd["visual.conv1.weight"]
     width, _, ps, _ = w.shape
     n = images.shape[0]
-    patches = F.unfold(images.float(), kernel_size=ps, stride=ps)        # [N, 3*ps*ps, G*G], (c,i,j) major
+    patches = F.unfold(images if images.dtype == torch.float64 else images.float(), kernel_size=ps, stride=ps)        # [N, 3*ps*ps, G*G], (c,i,j) major
     x = patches.transpose(1, 2) @ w.reshape(width, -1).t()               # [N, G*G, width]
     cls = sd["visual.class_embedding"].expand(n, 1, width)
     x = torch.cat([cls, x], dim=1) + sd["visual.positional_embedding"]

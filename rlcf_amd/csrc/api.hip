@@ -2,6 +2,7 @@
 // engine construction.  No torch types cross this boundary.
 #include "engine.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <cstdlib>
@@ -51,10 +52,27 @@ int rlcf_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* 
         char* buf = nullptr;
         RLCF_HIP_CHECK(hipMallocAsync((void**)&buf, 2 * ab + 2 * wb + 1024, st));
         void *ah = buf, *al = buf + ab, *wh = buf + 2 * ab, *wl = buf + 2 * ab + wb;
-        int rc = launch_split_f16x2(A, ah, al, (int64_t)M * K, st);
-        if (!rc) rc = launch_split_f16x2(W, wh, wl, (int64_t)N * K, st);
-        if (!rc) rc = launch_gemm_f16x3(ah, al, K, wh, wl, K, bias, residual, ldr, aux, ldaux, C, ldc, nullptr, nullptr, 0, M, N, K, alpha,
-                                        epilogue, st);
+        // each operand gets the exact power-of-two pre-scale of make_split (max|x| lifted into [2^9, 2^10), undone in alpha): operands
+        // of any finite range keep their 22 bits (f16 overflow above 65504, subnormal lo halves below 2^-3 otherwise); an infinite
+        // operand is refused rather than multiplied into a silent inf / NaN (a NaN element is not seen by the max — it propagates into
+        // the rows / columns it touches, as in the f32 path).  Reads max|A|, max|W| back to the host: blocks, not capturable.
+        float* amax = (float*)(buf + 2 * ab + 2 * wb);
+        int rc = launch_absmax(A, (int64_t)M * K, amax, st);
+        if (!rc) rc = launch_absmax(W, (int64_t)N * K, amax + 1, st);
+        float mx[2] = {0.f, 0.f};
+        if (!rc && (hipMemcpyAsync(mx, amax, sizeof(mx), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+            rc = RLCF_ERR_HIP;
+        if (!rc && !(std::isfinite(mx[0]) && std::isfinite(mx[1]))) {
+            rlcf_set_error("rlcf_gemm_nt: infinite operand (max|A| = %g, max|W| = %g)", mx[0], mx[1]);
+            rc = RLCF_ERR_ARG;
+        }
+        float sc[2] = {1.f, 1.f};
+        for (int i = 0; i < 2; ++i)
+            if (mx[i] > 0.f) sc[i] = std::ldexp(1.0f, std::max(-60, std::min(60, 9 - (int)std::floor(std::log2(mx[i])))));
+        if (!rc) rc = launch_split_f16x2(A, ah, al, (int64_t)M * K, st, sc[0]);
+        if (!rc) rc = launch_split_f16x2(W, wh, wl, (int64_t)N * K, st, sc[1]);
+        if (!rc) rc = launch_gemm_f16x3(ah, al, K, wh, wl, K, bias, residual, ldr, aux, ldaux, C, ldc, nullptr, nullptr, 0, M, N, K,
+                                        alpha / sc[0] / sc[1], epilogue, st);
         (void)hipFreeAsync(buf, st);
         return rc;
     }

@@ -117,12 +117,22 @@ def normal(seed: int, name: str, shape, std: float = 1.0, mean: float = 0.0,
     n = 1
     for s in shape:
         n *= int(s)
+    z = _z64(seed, name, n, device)
+    return (z * std + mean).to(torch.float32).reshape(*shape)
+
+
+def _z64(seed: int, name: str, n: int, device="cpu") -> torch.Tensor:
+    """the float64 standard scores behind ``normal`` (before its scale and fp32 rounding)"""
     acc = torch.zeros(n, dtype=torch.int64, device=device)
     for lane in range(4):
         w = raw_u32(seed, name, n, lane, device)
         acc += (w & 0xFFFF) + (w >> 16)
-    z = (acc.to(torch.float64) - 8 * 32767.5) / _IH_STD
-    return (z * std + mean).to(torch.float32).reshape(*shape)
+    return (acc.to(torch.float64) - 8 * 32767.5) / _IH_STD
+
+
+def _u64(seed: int, name: str, n: int, lane: int = 0) -> torch.Tensor:
+    """float64 uniforms in [0, 1) from the top 32 bits of stream (seed, name, lane), CPU (exact: a 32-bit integer over 2^32)"""
+    return raw_u32(seed, name, n, lane).to(torch.float64) / 4294967296.0
 
 
 def randint(seed: int, name: str, n: int, low: int, high: int, device="cpu") -> torch.Tensor:
@@ -151,11 +161,17 @@ def _block(sd, seed, prefix, width, layers, attn_std, proj_std, fc_std, device):
 
 
 def make_state_dict(geo: ClipGeometry, seed: int, device="cpu",
-                    logit_scale: float = math.log(100.0)) -> Dict[str, torch.Tensor]:
+                    logit_scale: float = math.log(100.0), profile: str = "init") -> Dict[str, torch.Tensor]:
     """fp32 state dict in the OpenAI CLIP key layout.  LayerNorm gains/biases and
     linear biases are non-trivial on purpose so every epilogue is exercised.
     ``logit_scale`` defaults to ln(100), the value of the released checkpoints
-    (a random-init CLIP has ln(1/0.07))."""
+    (a random-init CLIP has ln(1/0.07)).
+    ``profile``: "init" — init-scale Gaussians (every committed fixture depends on these bits); "trained" — the dynamic range of a
+    released checkpoint (``_trained``; built on the CPU and then moved to ``device``)."""
+    if profile == "trained":
+        return {k: v.to(device) for k, v in _trained(geo, seed, logit_scale).items()}
+    if profile != "init":
+        raise ValueError(f"profile {profile!r}: 'init' or 'trained'")
     sd: Dict[str, torch.Tensor] = {}
     vw, tw = geo.vision_width, geo.transformer_width
     if geo.is_resnet:
@@ -176,6 +192,144 @@ def make_state_dict(geo: ClipGeometry, seed: int, device="cpu",
     sd["visual.ln_post.bias"] = normal(seed, "v.lnpost_b", (vw,), 0.05, device=device)
     sd["visual.proj"] = normal(seed, "v.proj", (vw, geo.embed_dim), sc, device=device)
     _text(sd, seed, geo, device, logit_scale)
+    return sd
+
+
+# --------------------------------------------------------------------------
+# "trained" profile: the dynamic range of released CLIP weights
+# --------------------------------------------------------------------------
+
+N_MASSIVE = 3             # residual channels that carry "massive activations" (c_proj bias of +-100..300 in the first half of the blocks)
+QUIET_GAIN = 2.0 ** -7    # the last block's ln_2 gains and biases are scaled by this: rows of c_fc's operand below 2^-3
+LOUD_QK = 1.5             # the Q and K rows of head 0 of the first and last block are scaled by this: attention logits in the tens
+
+
+def massive_dims(seed: int, width: int) -> Tuple[int, ...]:
+    """the N_MASSIVE fixed residual channels of a tower of this width"""
+    out = []
+    for v in raw_u32(seed, "tr.massive", 64, 0).tolist():
+        if v % width not in out:
+            out.append(v % width)
+        if len(out) == N_MASSIVE:
+            return tuple(out)
+    raise AssertionError("unreachable")
+
+
+def _student_t(seed: int, name: str, shape, std: float) -> torch.Tensor:
+    """Student-t with nu = 3 scaled to standard deviation ``std``: z / sqrt(chi2_3 / 3) from four synth normal streams (chi2 gets a
+    floor of 0.03 so that a draw of exactly zero cannot divide by zero: |t| <= 49)."""
+    n = 1
+    for d in shape:
+        n *= int(d)
+    z = _z64(seed, name + "/t0", n)
+    chi = _z64(seed, name + "/t1", n) ** 2 + _z64(seed, name + "/t2", n) ** 2 + _z64(seed, name + "/t3", n) ** 2 + 0.03
+    t = z / torch.sqrt(chi / 3.0)
+    return (t * (std / math.sqrt(3.0))).to(torch.float32).reshape(*shape)
+
+
+def _pick(seed: int, name: str, width: int, n: int, avoid) -> list:
+    out = []
+    for v in raw_u32(seed, name + "/pick", 4 * n + 64, 0).tolist():
+        c = v % width
+        if c not in out and c not in avoid:
+            out.append(c)
+        if len(out) == n:
+            return out
+    raise AssertionError("unreachable")
+
+
+def _gain(seed: int, name: str, width: int, massive) -> torch.Tensor:
+    """LayerNorm gains: power of two times a uniform mantissa in [1, 2).  15 of 16 channels in [0.5, 2), one of 16
+    log-uniform over 2^-6 .. 2^5 (clamped to [0.02, 30]); two channels at each end of [0.02, 30] and two exact zeros."""
+    r = raw_u32(seed, name + "/e", width, 0)
+    tail = (r % 16) == 0
+    e = torch.where(tail, (r >> 3) % 11 - 6, (r >> 3) % 2 - 1)
+    g = torch.ldexp(1.0 + _u64(seed, name + "/m", width), e).clamp(0.02, 30.0)
+    lo1, lo2, hi1, hi2, z1, z2 = _pick(seed, name, width, 6, massive)
+    g[lo1], g[lo2], g[hi1], g[hi2], g[z1], g[z2] = 0.02, 0.021, 30.0, 29.0, 0.0, 0.0
+    for j, d in enumerate(massive):                        # the blocks' LayerNorms damp the massive channels (ln_pre lifts them)
+        g[d] = 0.0625 * (1.0 + float(_u64(seed, name + "/massive", len(massive))[j]))
+    return g.to(torch.float32)
+
+
+def _bias(seed: int, name: str, n: int, std: float, one_in: int) -> torch.Tensor:
+    """N(0, std) plus, on one entry in ``one_in``, a uniform offset in (-5, 5)"""
+    b = _z64(seed, name + "/b", n) * std
+    r = raw_u32(seed, name + "/s", n, 0)
+    big = (r % one_in) == 0
+    return torch.where(big, b + (_u64(seed, name + "/u", n) * 10.0 - 5.0), b).to(torch.float32)
+
+
+def _trained_tower(sd, seed, prefix, width, layers, proj_std, massive):
+    heads = width // 64
+    for i in range(layers):
+        p = f"{prefix}.resblocks.{i}."
+        w_in = _student_t(seed, p + "in_w", (3 * width, width), width ** -0.5)
+        if i in (0, layers - 1):                               # one loud head: q.k / 8 in the tens
+            w_in[0:64] *= LOUD_QK
+            w_in[width:width + 64] *= LOUD_QK
+        sd[p + "attn.in_proj_weight"] = w_in
+        sd[p + "attn.in_proj_bias"] = _bias(seed, p + "in_b", 3 * width, 0.02, 32)
+        sd[p + "attn.out_proj.weight"] = _student_t(seed, p + "out_w", (width, width), proj_std)
+        sd[p + "attn.out_proj.bias"] = _bias(seed, p + "out_b", width, 0.02, 32)
+        sd[p + "mlp.c_fc.weight"] = _student_t(seed, p + "fc_w", (4 * width, width), (2 * width) ** -0.5)
+        sd[p + "mlp.c_fc.bias"] = _bias(seed, p + "fc_b", 4 * width, 0.02, 32)
+        sd[p + "mlp.c_proj.weight"] = _student_t(seed, p + "proj_w", (width, 4 * width), proj_std)
+        cb = _bias(seed, p + "proj_b", width, 0.02, 32)
+        if i < max(1, layers // 2):                            # massive activations: +-100..300 on fixed residual channels
+            u = _u64(seed, p + "proj_b/massive", len(massive))
+            for j, d in enumerate(massive):
+                cb[d] = (1.0 if j % 2 == 0 else -1.0) * (100.0 + 200.0 * float(u[j]))
+        sd[p + "mlp.c_proj.bias"] = cb
+        for ln in ("ln_1", "ln_2"):
+            g = _gain(seed, p + ln + "_w", width, massive)
+            b = _bias(seed, p + ln + "_b", width, 0.05, 16)
+            if ln == "ln_2" and i == layers - 1:               # a quiet LayerNorm: its rows leave below 2^-3
+                bulk = torch.ldexp(1.0 + _u64(seed, p + "ln2_w/q", width), -(raw_u32(seed, p + "ln2_w/q", width, 1) % 2))
+                bulk[list(massive)] *= 0.0625
+                g, b = (bulk * QUIET_GAIN).to(torch.float32), (b.double() * QUIET_GAIN).to(torch.float32)
+            sd[p + ln + ".weight"], sd[p + ln + ".bias"] = g, b
+
+
+def _trained(geo: ClipGeometry, seed: int, logit_scale: float) -> Dict[str, torch.Tensor]:
+    """The "trained" profile: released CLIP weights are far from init scale, and the kernels' number formats are chosen for O(1) data
+    (split-f16 operands, one-pass row statistics, exp / rcp fast forms).  This profile reproduces the dynamic range of a trained
+    ViT + text transformer on the seeded generator, deterministic from (seed, name):
+      * Linear / in_proj / out_proj / projection / patch-embedding weights: Student-t (nu = 3) at the init standard deviation;
+      * LayerNorm gains: power of two times a uniform mantissa, one channel in 16 log-uniform over [0.02, 30], two channels at each
+        end of that range, two exact zeros, 0.0625..0.125 on the massive channels (ln_pre: 24..30); biases N(0, 0.05) with one entry in 16 offset by up to +-5
+        (ln_post / ln_final: N(0, 0.05) alone); Linear biases likewise (1 in 32);
+      * massive activations: the c_proj bias of the first half of every tower's blocks is +-100..300 on ``massive_dims`` (ln_pre gains
+        of 24..30 on the same channels);
+      * attention: head 0 of the first and last block has its Q and K rows scaled by LOUD_QK (logits in the tens);
+      * the last block's ln_2 is quiet (gains and bias times QUIET_GAIN): c_fc operand rows below 2^-3;
+      * class / positional / token embeddings at 4x (text positional 5x) the init standard deviation; logit_scale as given (ln 100).
+    Built on the CPU in float64 (integer hashes; +, -, *, /, sqrt, exact ldexp) and rounded once to fp32; make_state_dict moves it to
+    the device, so CPU and GPU tests see the same bits.  ModifiedResNet image towers are out of scope (their activations already go
+    through the device-side dynamic scale of the split-f16 GEMM): such geometries raise."""
+    if geo.is_resnet:
+        raise ValueError("the trained profile covers VisionTransformer image towers and text towers only")
+    sd = make_state_dict(geo, seed, "cpu", logit_scale)
+    vw, tw, ps = geo.vision_width, geo.transformer_width, geo.vision_patch_size
+    sc = vw ** -0.5
+    vm = massive_dims(seed, vw)
+    sd["visual.conv1.weight"] = _student_t(seed, "v.conv1", (vw, 3, ps, ps), (3 * ps * ps) ** -0.5)
+    sd["visual.class_embedding"] = normal(seed, "v.cls", (vw,), 4 * sc)
+    sd["visual.positional_embedding"] = normal(seed, "v.pos", (geo.vision_tokens, vw), 4 * sc)
+    g = _gain(seed, "v.lnpre_w", vw, vm)
+    for j, d in enumerate(vm):
+        g[d] = 24.0 + 6.0 * float(_u64(seed, "v.lnpre_w/massive", len(vm))[j])
+    sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"] = g, _bias(seed, "v.lnpre_b", vw, 0.05, 16)
+    _trained_tower(sd, seed, "visual.transformer", vw, geo.vision_layers, sc * (2 * geo.vision_layers) ** -0.5, vm)
+    sd["visual.ln_post.weight"] = _gain(seed, "v.lnpost_w", vw, vm)       # (ln_post / ln_final biases keep init scale: a +-5 entry there
+    sd["visual.ln_post.bias"] = normal(seed, "v.lnpost_b", (vw,), 0.05)     # would be one constant direction of every feature)
+    sd["visual.proj"] = _student_t(seed, "v.proj", (vw, geo.embed_dim), sc)
+    tm = massive_dims(seed, tw)
+    sd["token_embedding.weight"] = normal(seed, "t.tok", (geo.vocab_size, tw), 0.08)
+    sd["positional_embedding"] = normal(seed, "t.pos", (geo.context_length, tw), 0.05)
+    _trained_tower(sd, seed, "transformer", tw, geo.transformer_layers, (tw ** -0.5) * (2 * geo.transformer_layers) ** -0.5, tm)
+    sd["ln_final.weight"], sd["ln_final.bias"] = _gain(seed, "t.lnf_w", tw, tm), normal(seed, "t.lnf_b", (tw,), 0.05)
+    sd["text_projection"] = _student_t(seed, "t.proj", (tw, geo.embed_dim), tw ** -0.5)
     return sd
 
 

@@ -318,6 +318,9 @@ def test_synth_generator_bit_identical_on_gpu(L, dev, geo):
         else:
             assert torch.equal(a[k], b[k].cpu()), k
     assert torch.equal(synth.make_views(1000, 5, g.image_resolution), synth.make_views(1000, 5, g.image_resolution, device=dev).cpu())
+    if not g.is_resnet:              # the trained profile (built on the CPU, moved to the device) carries the same bits too
+        a, b = synth.make_state_dict(g, 11, profile="trained"), synth.make_state_dict(g, 11, device=dev, profile="trained")
+        assert a.keys() == b.keys() and all(torch.equal(a[k], b[k].cpu()) for k in a)
 
 
 @pytest.mark.parametrize("geo", ["tiny", "small"])

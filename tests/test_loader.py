@@ -125,3 +125,35 @@ def test_params_mirror_has_every_reference_flag_with_its_default():
                   "--tta_steps", "3", "--sample_k", "3", "--reward_arch", "ViT-L/14", "--reward_amplify", "0", "--reward_process", "1",
                   "--process_batch", "0", "--weight_decay", "5e-4", "--selection_p", "0.1", "--output", "/tmp/x", "--multiple_reward_models", "0"])
     assert (a.arch, a.batch_size, a.tta_steps, a.sample_k, a.augmix, a.hard_aug) == ("ViT-B/16", 64, 3, 3, 1, 0)
+
+
+@pytest.mark.parametrize("form", ["dict", "jit"])
+def test_load_fp16_stored_trained_archive(tmp_path, form):
+    """An archive as OpenAI ships it: the Conv / Linear / attention / projection tensors STORED as fp16 (convert_weights, model.py:375-396),
+    here of the trained weight profile (synth.make_state_dict(profile="trained")).  load() hands back float32 tensors equal to the fp16
+    values exactly — the state dict synth.to_fp16_grid describes, which the engine runs in its two-pass form."""
+    geo = synth.GEOMETRIES["tiny"]
+    sd32 = synth.make_state_dict(geo, 11, profile="trained")
+    grid = synth.to_fp16_grid(sd32)
+    keys = _FP16_KEYS(sd32)
+    stored = {k: (v.half() if k in keys else v) for k, v in sd32.items()}
+    assert sum(v.dtype == torch.float16 for v in stored.values()) > 10
+    name = f"unit/fp16-{form}"
+    path = os.path.join(tmp_path, name.replace("/", "-") + ".pt")
+    if form == "dict":
+        torch.save(stored, path)
+    else:
+        torch.jit.script(_module_tree(stored)).save(path)
+    ckpt, _, _ = clip_store.load(name, device="cpu", download_root=str(tmp_path))
+    assert set(ckpt.state_dict) == set(sd32)
+    for k, v in stored.items():
+        got = ckpt.state_dict[k]
+        assert got.dtype == torch.float32, k
+        assert torch.equal(got, v.float()) and torch.equal(got, grid[k]), k
+
+
+def _FP16_KEYS(sd):
+    """the keys to_fp16_grid rounds (and convert_weights stores as fp16)"""
+    probe = {k: (v + 2.0 ** -20 if v.is_floating_point() else v) for k, v in sd.items()}
+    g = synth.to_fp16_grid(probe)
+    return {k for k in sd if not torch.equal(g[k], probe[k])}
