@@ -196,7 +196,10 @@ int rlcf_entropy_select(const float* logits, int n, int C, int n_sel, float* ent
 /* Flags of rlcf_reward_loss (TPT/params.py:55-59,65-66). */
 #define RLCF_MAX_REWARDS 4
 enum { RLCF_F_REWARD_PROCESS = 1, RLCF_F_AMPLIFY = 2, RLCF_F_PROCESS_BATCH = 4, RLCF_F_MIN_ENTROPY = 8,
-       RLCF_F_NO_SELECTION = 16 /* image-encoder tuning calls: rows taken in order, no confidence selection (set by rlcf_tta_retrieval_image) */ };
+       RLCF_F_NO_SELECTION = 16 /* image-encoder tuning calls: rows taken in order, no confidence selection (set by rlcf_tta_retrieval_image) */,
+       /* (ABI version 15) the loss kind of an image-encoder tuning call, a 2-bit field: 0 = the RL reward loss above; otherwise the
+        * distillation loss of TPT/tune_cls_kd.py:48-55 against the reward model's logits (rlcf_kd_loss, mode = field >> 5) */
+       RLCF_F_KD = 32, RLCF_F_DKD = 64, RLCF_F_ATKD = 96, RLCF_F_KD_MASK = 96 };
 /* The loss section of test_time_tuning (TPT/tpt_cls_rl.py:63-74) with
  * CLIPRewards.CLIPScore / rewards_post_process (TPT/clip_reward.py:111-128,152-165):
  * rows = logits[sel[i]] (sel NULL: rows = logits[i]); top-K classes per row; CLIPScore
@@ -220,6 +223,22 @@ int rlcf_reward_loss_ensemble(const float* logits, int ld_logits, const int32_t*
                               int mean, float clipscore_weight, int flags, float min_entropy_w,
                               int32_t* topk_idx, float* clip_score, float* rewards, float* loss, float* dlogits,
                               rlcf_stream stream);
+
+/* (ABI version 15) Distillation losses of the KD ablation (TPT/tune_cls_kd.py:34-61): student rows [n, C] (row stride ld_s)
+ * against teacher rows [n, C] (ld_t), loss = mean over rows of
+ *   RLCF_KD_KD   kd_distill_loss_v2 (TPT/utils/KD.py:19-29):  -T_stu^2 * sum_c softmax(t/T_tea)_c * log_softmax(s/T_stu)_c
+ *   RLCF_KD_DKD  dkd_distill_loss (TPT/utils/DKD.py:13-37): T^2 * (alpha * TCKD + beta * NCKD) around target[i] (NULL = the teacher's
+ *                argmax, first maximum on ties); the NCKD softmaxes exclude the target class (the reference's -1000 shift)
+ *   RLCF_KD_ATKD atkd_distill_loss version 1 (TPT/utils/ATKD.py:12-42), with the reference's swapped torch.std_mean unpacking:
+ *                rows normalised as (z - std(z)) / (mean(z) + eps) * multiplier, per-row KL scaled by mean(student)^2
+ * params NULL = the reference's defaults (T_stu = T_tea = 1, alpha 1, beta 0.5, temperature 1, multiplier 2, eps 1e-5).
+ * Outputs (each optional, at least one): loss [1], row_loss [n] (the per-row terms before the mean), dlogits [n, C] = d loss /
+ * d student (dense; the teacher is a constant).  One workgroup per row, fixed-order reductions: bit-reproducible.
+ * 1 <= C <= RLCF_KD_MAX_CLASSES.  Scratch from the stream-ordered allocator of `stream`. */
+enum { RLCF_KD_KD = 1, RLCF_KD_DKD = 2, RLCF_KD_ATKD = 3, RLCF_KD_MAX_CLASSES = 65536 };
+typedef struct { float T_stu, T_tea, alpha, beta, temperature, multiplier, eps; } rlcf_kd_params;
+int rlcf_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, int mode, const int32_t* target,
+                 const rlcf_kd_params* params, float* loss, float* row_loss, float* dlogits, rlcf_stream stream);
 
 /* torch.optim.AdamW single step (amsgrad off), TPT/tpt_cls_rl.py:78,120. step is 1-based. */
 int rlcf_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, int step,

@@ -19,6 +19,9 @@ TEXT_DENSE, TEXT_PACKED, TEXT_SHARED = 0, 1, 2
 STUDENT, REWARD = 0, 1
 MAX_REWARDS = 4
 F_REWARD_PROCESS, F_AMPLIFY, F_PROCESS_BATCH, F_MIN_ENTROPY = 1, 2, 4, 8
+F_KD, F_DKD, F_ATKD, F_KD_MASK = 32, 64, 96, 96          # loss kind of the image-encoder tuning calls (0 = the RL reward loss)
+KD_KD, KD_DKD, KD_ATKD = 1, 2, 3                          # rlcf_kd_loss modes (= the flag field >> 5)
+KD_MAX_CLASSES = 65536
 
 
 class ClipCfg(C.Structure):
@@ -50,6 +53,10 @@ class TTAArgs(C.Structure):
                 ("eps", C.c_float), ("flags", C.c_int), ("clipscore_weight", C.c_float),
                 ("min_entropy_w", C.c_float), ("sparse_backward", C.c_int), ("skip_final", C.c_int),
                 ("ctx_in", C.c_void_p), ("n_sel", C.c_int)]
+
+
+class KdParams(C.Structure):   # rlcf_kd_params: hyper-parameters of the three distillation losses
+    _fields_ = [(n, C.c_float) for n in ("T_stu", "T_tea", "alpha", "beta", "temperature", "multiplier", "eps")]
 
 
 TTA_OUT_FIELDS = ("logits", "entropy", "selected_idx", "topk_idx", "clip_score", "rewards", "loss", "dlogits",
@@ -86,6 +93,7 @@ SIGNATURES = {
     "rlcf_attention_bwd": (I, [P, P, P, I, I, I, I, P, P]),
     "rlcf_entropy_select": (I, [P, I, I, I, P, P, P]),
     "rlcf_reward_loss": (I, [P, I, P, I, I, I, P, P, I, F, I, F, P, P, P, P, P, P]),
+    "rlcf_kd_loss": (I, [P, I, P, I, I, I, I, P, C.POINTER(KdParams), P, P, P, P]),
     "rlcf_adamw_step": (I, [P, P, P, P, I64, I, F, F, F, F, F, P]),
     "rlcf_engine_create": (P, [C.POINTER(ClipCfg), C.POINTER(ClipCfg), I, I, I]),
     "rlcf_engine_destroy": (None, [P]),

@@ -35,7 +35,7 @@ int rlcf_func_lds(const void* fn, size_t bytes) {
 extern "C" {
 
 const char* rlcf_last_error(void) { return g_err; }
-int rlcf_version(void) { return 14; }   // 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
+int rlcf_version(void) { return 15; }   // 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
 //    // 2: rlcf_clip_cfg.vision_stages, reward slots, views, LN batch; 3: rlcf_tta_out.vis_*, rlcf_tta_sample_visual
 
 // ------------------------------------------------------------------ op level
@@ -438,6 +438,25 @@ int rlcf_logits(rlcf_engine* e, const float* img, int n, const float* txt, int C
     RLCF_ARG_CHECK(e && img && txt && logits && n > 0 && C > 0);
     return engine_logits(e, img, n, txt, C, logits, engine_stream(e, stream));
 }
+int rlcf_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, int mode, const int32_t* target,
+                 const rlcf_kd_params* params, float* loss, float* row_loss, float* dlogits, rlcf_stream stream) {
+    RLCF_ARG_CHECK(student && teacher);
+    if (n <= 0) { rlcf_set_error("kd_loss: n = %d rows", n); return RLCF_ERR_ARG; }
+    double* acc = nullptr;           // stateless call: the per-row sums come from the stream-ordered allocator
+    RLCF_HIP_CHECK(hipMallocAsync((void**)&acc, (size_t)n * sizeof(double), (hipStream_t)stream));
+    const int rc = launch_kd_loss(student, ld_s, teacher, ld_t, n, C, mode, target, params, loss, row_loss, dlogits, acc, (hipStream_t)stream);
+    (void)hipFreeAsync(acc, (hipStream_t)stream);
+    return rc;
+}
+// the distillation loss kinds exist only on the one-image image-encoder tuning calls (tune_cls_kd.py has no prompt, batched, lane
+// or retrieval form)
+static int kd_refused(const rlcf_tta_args* a, const char* entry) {
+    if (a && (a->flags & RLCF_F_KD_MASK)) {
+        rlcf_set_error("%s: the distillation losses (RLCF_F_KD / DKD / ATKD) run on rlcf_tta_sample_ln / rlcf_tta_sample_visual only", entry);
+        return RLCF_ERR_ARG;
+    }
+    return RLCF_OK;
+}
 int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img, int n, const float* dlogits, float* dctx,
                              rlcf_stream stream) {
     RLCF_ARG_CHECK(e && ctx && img && dlogits && dctx && n > 0);
@@ -445,6 +464,7 @@ int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img,
 }
 int rlcf_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_sample")) return rc_;
     return engine_tta_sample(e, views, N, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
@@ -457,6 +477,7 @@ int rlcf_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rlcf
 }
 int rlcf_tta_retrieval_image(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && images && args && n > 0);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_image")) return rc_;
     rlcf_tta_args a = *args;
     a.selection_p = 1.0f; a.n_sel = n; a.flags |= RLCF_F_NO_SELECTION;     // every query image carries reward and gradient, in loader order
     return engine_tta_sample_visual(e, images, n, &a, out, engine_stream(e, stream));
@@ -467,6 +488,7 @@ int rlcf_engine_set_image_bank(rlcf_engine* e, const float* student_feats, const
 }
 int rlcf_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && tokens_host && args);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_text")) return rc_;
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream));
 }
 int64_t rlcf_engine_text_param_count(rlcf_engine* e, int* ln_count, rlcf_stream stream) {
@@ -683,11 +705,13 @@ int rlcf_engine_reset_visual_state(rlcf_engine* e, rlcf_stream stream) {
 int rlcf_tta_batch(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                    rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_batch")) return rc_;
     return engine_tta_batch(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
 int rlcf_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                       rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_batch_ln")) return rc_;
     return engine_tta_batch_ln(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
 // ------------------------------------------------------------------ samples in flight (ABI 14)
@@ -755,6 +779,7 @@ rlcf_stream rlcf_lanes_stream(const rlcf_lanes* l, int k) { return (l && k >= 0 
 int rlcf_lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                       int norm_layers, rlcf_stream producer) {
     RLCF_ARG_CHECK(l && views && args && count > 0 && top5);
+    if (const int rc_ = kd_refused(args, "rlcf_lanes_submit")) return rc_;
     const int k = l->next;
     RLCF_HIP_CHECK(hipEventRecord(l->ready, (hipStream_t)producer));
     RLCF_HIP_CHECK(hipStreamWaitEvent(l->st[k], l->ready, 0));
@@ -773,6 +798,7 @@ int rlcf_lanes_join(rlcf_lanes* l, rlcf_stream consumer) {
 int rlcf_tta_lanes(rlcf_engine* const* engines, int lanes, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits,
                    int32_t* top5, int norm_layers, rlcf_stream stream) {
     RLCF_ARG_CHECK(engines && lanes >= 1 && views && args && count > 0 && top5);
+    if (const int rc_ = kd_refused(args, "rlcf_tta_lanes")) return rc_;
     rlcf_lanes* l = rlcf_lanes_create(engines, lanes);
     if (!l) return RLCF_ERR_HIP;
     const rlcf_clip_cfg& c = engines[0]->model[RLCF_STUDENT].cfg;

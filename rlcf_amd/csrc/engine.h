@@ -239,6 +239,7 @@ struct rlcf_engine {
     // rlcf_engine_destroy waits for, instead of the whole device
     std::vector<hipStream_t> used_streams;
     DevBuf rl_stats;                 // per-row scratch of the reward / loss kernels
+    DevBuf kd_teacher;               // [n_sel, C] the reward model's logits of the selected views (distillation losses, step 0 on)
     DevBuf step_skip;                // int32 per test sample: gradient held an inf / NaN -> optimizer step skipped (GradScaler semantics)
     // packed class-sequence runs of the text pass being enqueued (set by text_forward around transformer_forward)
     const rlcf_seq* pk_cur = nullptr; int n_pk_cur = 0; const int32_t* rss_cur = nullptr;

@@ -157,6 +157,37 @@ int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, co
     return RLCF_OK;
 }
 
+// ------------------------------------------------------------------ distillation losses (TPT/tune_cls_kd.py:34-61)
+// The KD ablation adapts the same student with the same frozen CLIP, the reward loss replaced by a distillation loss against the
+// reward model's logits of the selected views; selection, backward, step skip and AdamW are the RL path's.
+static int kd_mode(const rlcf_tta_args* a) { return (a->flags & RLCF_F_KD_MASK) >> 5; }
+static int kd_check(const rlcf_engine* e, const rlcf_tta_args* a) {
+    if (!kd_mode(a)) return RLCF_OK;
+    if (a->flags & (RLCF_F_MIN_ENTROPY | RLCF_F_NO_SELECTION)) {
+        rlcf_set_error("the distillation losses take no min-entropy regulariser and no retrieval rows (flags 0x%x)", a->flags);
+        return RLCF_ERR_ARG;
+    }
+    if (e->n_rewards != 1) {        // CLIPRewardsMultiple has no calulate_similarity (clip_reward.py:180-307): KD needs one reward model
+        rlcf_set_error("the distillation losses need exactly one reward model (the engine holds %d)", e->n_rewards);
+        return RLCF_ERR_ARG;
+    }
+    return RLCF_OK;
+}
+// reward_model.calulate_similarity() on the selected views (tune_cls_kd.py:45-46, clip_reward.py:168-177):
+// r_logits_per_image = exp(reward.logit_scale) * reward_image_features @ reward_class_features^T, computed once at step 0
+static int kd_teacher(rlcf_engine* e, int n_sel, hipStream_t st) {
+    const ClipModel& r = e->model[RLCF_REWARD];
+    const int Dr = r.cfg.embed_dim, C = e->C;
+    TRY(e->kd_teacher.ensure((size_t)n_sel * C * sizeof(float)));
+    return gemm(e, e->rimg[0].as<float>(), Dr, e->reward_cls[0].as<float>(), Dr, nullptr, nullptr, 0, nullptr, 0, e->kd_teacher.as<float>(), C,
+                n_sel, C, Dr, r.logit_scale_exp, RLCF_EPI_NONE, st);
+}
+// loss and dlogits of one step (tune_cls_kd.py:48-55) into e->loss / e->dlogits, where the reward loss leaves them
+static int kd_step(rlcf_engine* e, int n_sel, const rlcf_tta_args* a, hipStream_t st) {
+    return launch_kd_loss(e->sel_logits.as<float>(), e->C, e->kd_teacher.as<float>(), e->C, n_sel, e->C, kd_mode(a), nullptr, nullptr,
+                          e->loss.as<float>(), nullptr, e->dlogits.as<float>(), (double*)e->rl_stats.p, st);
+}
+
 // ------------------------------------------------------------------ BatchNorm tuning of a ModifiedResNet student
 // One iteration of tune_cls_rl.py:183-256 with CLIPCLS_TTA(arch=RN*, only_norm=True): the tuned tensors are the weight / bias of every
 // BatchNorm2d whose name contains 'bn' (custom_clip.py:481-485: the downsample BatchNorms stay frozen).  The tuning passes run the
@@ -184,6 +215,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
     const size_t vb = full ? e->vw_count * sizeof(float) : 0;
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
+    const bool kd = kd_mode(a) != 0;
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const size_t nb = (size_t)e->ln_count * sizeof(float);
     const rlcf_tta_out none{};
@@ -212,6 +244,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
             TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (kd) TRY(kd_teacher(e, n_sel, st));
             TRY(launch_gather_rows(e->logits.as<float>(), C, e->sel_idx.as<int32_t>(), e->sel_logits.as<float>(), C, n_sel, C, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
             COPY_OUT(out->entropy, e->entropy.p, N * sizeof(float));
@@ -219,7 +252,8 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         } else {
             TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
         }
-        TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
+        if (kd) TRY(kd_step(e, n_sel, a, st));
+        else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
         if (j == 0) {
@@ -233,9 +267,11 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         TRY(rn_backward_bn(e, s, n, e->ln_feat.as<float>(), e->dfeat.as<float>(), e->ln_grad.as<float>(), st, full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-            COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-            COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            if (!kd) {           // (the distillation losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
+                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
+                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
+                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            }
             COPY_OUT(out->loss, e->loss.p, sizeof(float));
             COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
             COPY_OUT(out->ln_grad, e->ln_grad.p, nb);
@@ -289,6 +325,8 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
+    TRY(kd_check(e, a));
+    const bool kd = kd_mode(a) != 0;
     if (is_resnet(s.cfg)) {
         return engine_tta_sample_bn(e, views, N, a, out, st, full);
     }
@@ -319,13 +357,15 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
             if (a->flags & RLCF_F_NO_SELECTION) TRY(launch_iota(e->sel_idx.as<int32_t>(), n_sel, st));     // retrieval: every row, in order
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
             TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (kd) TRY(kd_teacher(e, n_sel, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
             COPY_OUT(out->entropy, e->entropy.p, N * sizeof(float));
             COPY_OUT(out->selected_idx, e->sel_idx.p, n_sel * sizeof(int32_t));
         }
         TRY(vit_forward_saved(e, s, e->views_sel.as<float>(), n_sel, e->ln_feat.as<float>(), st));
         TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
-        TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
+        if (kd) TRY(kd_step(e, n_sel, a, st));
+        else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
         if (full) RLCF_HIP_CHECK(hipMemsetAsync(e->vw_grad.p, 0, vb, st));
@@ -333,9 +373,11 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
                             full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-            COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-            COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            if (!kd) {           // (the distillation losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
+                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
+                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
+                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            }
             COPY_OUT(out->loss, e->loss.p, sizeof(float));
             COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
             COPY_OUT(out->ln_grad, e->ln_grad.p, nb);

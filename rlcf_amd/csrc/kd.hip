@@ -1,0 +1,246 @@
+// Distillation losses of the KD ablation (TPT/tune_cls_kd.py:34-61): the student's logits rows against the reward model's
+// (teacher) logits rows, the loss and its dense gradient d loss / d student.  Three losses, called as tune_cls_kd.py calls them:
+//   KD   kd_distill_loss_v2 (TPT/utils/KD.py:19-29)    row = -T_s^2 * sum_c pt_c * log_softmax(s / T_s)_c,  pt = softmax(t / T_t)
+//   DKD  dkd_distill_loss   (TPT/utils/DKD.py:13-37)   row = T^2 * (alpha * TCKD + beta * NCKD), target g = teacher argmax
+//   ATKD atkd_distill_loss  (TPT/utils/ATKD.py:12-42)  version 1, see the note on its statistics below
+// loss = mean over rows.  One workgroup per row, every reduction a fixed-order wave-shuffle + LDS tree, the row mean a serial
+// sum: two calls give bit-identical results (no atomics).  The row arithmetic runs in double (n_sel x C = 6 x 1000 elements
+// on the tuning path: the cost is nil), so the float results are the float64 values rounded once.
+//
+// Gradients (derived by hand, z = the row as the loss normalises it, ps = softmax(z_s), pt = the teacher's distribution;
+// sum(pt) is kept literal, as the autograd of log_softmax keeps it):
+//   KD:   d/ds_c = T_s^2 * (1/T_s) * (ps_c * sum(pt) - pt_c) / n = T_s * (ps_c * sum(pt) - pt_c) / n
+//   ATKD: z_s = (s - a) * k with k = multiplier / (b + eps) and the statistics a, b held constant (no_grad), row scaled by b^2:
+//         d/ds_c = b^2 * k * (ps_c * sum(pt) - pt_c) / n
+//   DKD:  TCKD = KL([pt_g, pt_o] || [ps_g, ps_o]) with ps_o = sum_{c != g} ps_c (summed, not 1 - ps_g, as cat_mask sums it):
+//           dTCKD/dz_g = ps_g * (pt_g + pt_o) - pt_g
+//           dTCKD/dz_c = ps_c * (pt_g + pt_o) - pt_o * qs_c           (c != g; ps_c / ps_o = qs_c, the NCKD softmax below)
+//         NCKD = KL(qt || qs), q = softmax over the classes c != g: the reference pushes the target logit down by 1000, whose
+//         exp underflows to exactly 0 for CLIP-range logits, so the target class is excluded here outright:
+//           dNCKD/dz_c = qs_c * sum(qt) - qt_c  (c != g),  0 at c = g
+//         d/ds_c = T * (alpha * dTCKD/dz_c + beta * dNCKD/dz_c) / n
+//         torch.log of the merged pair is -inf when ps_g or ps_o is 0 in float32 (the reference's precision): that row then
+//         gets loss +inf and NaN gradients, as the reference's autograd gives them, and the GradScaler step skip follows.
+#include "kernels.h"
+
+#define KD_THREADS 256
+
+__device__ __forceinline__ double kd_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double kd_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double kd_block_sum(double v, double* red) {
+    v = kd_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int i = 0; i < KD_THREADS / 64; ++i) s += red[i];
+    return s;
+}
+__device__ __forceinline__ double kd_block_max(double v, double* red) {
+    v = kd_wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = red[0];
+    for (int i = 1; i < KD_THREADS / 64; ++i) s = fmax(s, red[i]);
+    return s;
+}
+// torch.argmax: first maximum, NaN ranks highest
+__device__ __forceinline__ bool kd_better(float a, int ia, float b, int ib) {
+    if (a != a) return b == b || ia < ib;
+    if (b != b) return false;
+    return a > b || (a == b && ia < ib);
+}
+__device__ int kd_block_argmax(const float* x, int C, float* redv, int* redi) {
+    float v = -INFINITY;
+    int i = C;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS)
+        if (kd_better(x[c], c, v, i)) { v = x[c]; i = c; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (kd_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { redv[threadIdx.x >> 6] = v; redi[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    v = redv[0]; i = redi[0];
+    for (int w = 1; w < KD_THREADS / 64; ++w)
+        if (kd_better(redv[w], redi[w], v, i)) { v = redv[w]; i = redi[w]; }
+    return i;
+}
+// population mean and standard deviation of a row (torch.std_mean(unbiased=False)), two passes
+__device__ void kd_row_stats(const float* x, int C, double* red, double& mean, double& std) {
+    double s = 0.0;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS) s += (double)x[c];
+    mean = kd_block_sum(s, red) / C;
+    double q = 0.0;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS) { const double d = (double)x[c] - mean; q += d * d; }
+    std = sqrt(kd_block_sum(q, red) / C);
+}
+// p * (log p - lq) with torch.kl_div's convention 0 * log 0 = 0
+__device__ __forceinline__ double kd_kl_term(double p, double lp, double lq) { return p > 0.0 ? p * (lp - lq) : 0.0; }
+
+__global__ __launch_bounds__(KD_THREADS) void kd_rows_kernel(const float* __restrict__ stu, int ld_s, const float* __restrict__ tea, int ld_t,
+                                                             int C, int mode, const int32_t* __restrict__ target, rlcf_kd_params p, double inv_n,
+                                                             double* __restrict__ row_acc, float* __restrict__ row_loss, float* __restrict__ dlogits) {
+    __shared__ double red[KD_THREADS / 64];
+    __shared__ float redv[KD_THREADS / 64];
+    __shared__ int redi[KD_THREADS / 64];
+    const int i = blockIdx.x;
+    const float* x = stu + (size_t)i * ld_s;
+    const float* y = tea + (size_t)i * ld_t;
+    float* d = dlogits ? dlogits + (size_t)i * C : nullptr;
+    // z = (v - shift) * scale for both rows
+    double ks = 1.0, kt = 1.0, as = 0.0, at = 0.0, out_scale = 1.0, grad_scale = 1.0;
+    if (mode == RLCF_KD_KD) {
+        ks = 1.0 / (double)p.T_stu; kt = 1.0 / (double)p.T_tea;
+        out_scale = (double)p.T_stu * (double)p.T_stu;
+        grad_scale = out_scale * ks;
+    } else if (mode == RLCF_KD_DKD) {
+        ks = kt = 1.0 / (double)p.temperature;
+        out_scale = (double)p.temperature * (double)p.temperature;
+        grad_scale = out_scale * ks;
+    } else {
+        // ATKD version 1.  utils/ATKD.py:21-22 unpack torch.std_mean (which returns (std, mean)) as `s_mu, s_std`: the row is
+        // normalised as (z - std(z)) / (mean(z) + eps) * multiplier and the KL is scaled by mean(z)^2.  Reproduced literally.
+        double ms, ss, mt, sd;
+        kd_row_stats(x, C, red, ms, ss);
+        kd_row_stats(y, C, red, mt, sd);
+        as = ss; ks = (double)p.multiplier / (ms + (double)p.eps);
+        at = sd; kt = (double)p.multiplier / (mt + (double)p.eps);
+        out_scale = ms * ms;
+        grad_scale = out_scale * ks;
+    }
+    int g = -1;
+    if (mode == RLCF_KD_DKD) {
+        g = target ? target[i] : kd_block_argmax(y, C, redv, redi);
+        if (g < 0 || g >= C) {                               // out-of-range target: NaN row (nothing is read outside the row)
+            if (threadIdx.x == 0) { row_acc[i] = NAN; if (row_loss) row_loss[i] = NAN; }
+            if (d) for (int c = threadIdx.x; c < C; c += KD_THREADS) d[c] = NAN;
+            return;
+        }
+    }
+    // maxima (DKD: also over the non-target classes, the shift of the NCKD softmaxes)
+    double mxs = -INFINITY, mxt = -INFINITY, mxs_n = -INFINITY, mxt_n = -INFINITY;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+        const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+        mxs = fmax(mxs, zs); mxt = fmax(mxt, zt);
+        if (c != g) { mxs_n = fmax(mxs_n, zs); mxt_n = fmax(mxt_n, zt); }
+    }
+    mxs = kd_block_max(mxs, red); mxt = kd_block_max(mxt, red);
+    if (mode == RLCF_KD_DKD) { mxs_n = kd_block_max(mxs_n, red); mxt_n = kd_block_max(mxt_n, red); }
+    double ss = 0.0, st = 0.0, ss_n = 0.0, st_n = 0.0;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+        const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+        ss += exp(zs - mxs); st += exp(zt - mxt);
+        if (mode == RLCF_KD_DKD && c != g) { ss_n += exp(zs - mxs_n); st_n += exp(zt - mxt_n); }
+    }
+    ss = kd_block_sum(ss, red); st = kd_block_sum(st, red);
+    const double lss = log(ss), lst = log(st);
+    if (mode == RLCF_KD_DKD) { ss_n = kd_block_sum(ss_n, red); st_n = kd_block_sum(st_n, red); }
+    const double lss_n = log(ss_n), lst_n = log(st_n);
+    if (mode != RLCF_KD_DKD) {
+        // KD: -sum pt * log ps;  ATKD: sum pt * (log pt - log ps)
+        double l = 0.0, spt = 0.0;
+        for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+            const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+            const double lps = zs - mxs - lss, lpt = zt - mxt - lst, pt = exp(lpt);
+            l += mode == RLCF_KD_KD ? -pt * lps : kd_kl_term(pt, lpt, lps);
+            spt += pt;
+        }
+        l = kd_block_sum(l, red) * out_scale;
+        spt = kd_block_sum(spt, red);
+        if (threadIdx.x == 0) { row_acc[i] = l; if (row_loss) row_loss[i] = (float)l; }
+        if (d) {
+            const double gs = grad_scale * inv_n;
+            for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+                const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+                d[c] = (float)(gs * (exp(zs - mxs - lss) * spt - exp(zt - mxt - lst)));
+            }
+        }
+        return;
+    }
+    // DKD: the merged pair [p_g, p_other] of both rows; p_other summed over the non-target probabilities (cat_mask)
+    double ps_o = 0.0, pt_o = 0.0, nckd = 0.0, sqt = 0.0;
+    for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+        if (c == g) continue;
+        const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+        ps_o += exp(zs - mxs - lss); pt_o += exp(zt - mxt - lst);
+        const double lqs = zs - mxs_n - lss_n, lqt = zt - mxt_n - lst_n, qt = exp(lqt);
+        nckd += kd_kl_term(qt, lqt, lqs);
+        sqt += qt;
+    }
+    ps_o = kd_block_sum(ps_o, red); pt_o = kd_block_sum(pt_o, red);
+    nckd = kd_block_sum(nckd, red); sqt = kd_block_sum(sqt, red);
+    const double zsg = ((double)x[g] - as) * ks, ztg = ((double)y[g] - at) * kt;
+    const double lps_g = zsg - mxs - lss, lpt_g = ztg - mxt - lst, ps_g = exp(lps_g), pt_g = exp(lpt_g);
+    // torch.log(pred_student) of the reference (float32): -inf when either merged probability is 0 there
+    const bool dead = (float)ps_g == 0.f || (float)ps_o == 0.f;
+    const double tckd = kd_kl_term(pt_g, lpt_g, lps_g) + kd_kl_term(pt_o, log(pt_o), log(ps_o));
+    const double l = dead ? INFINITY : out_scale * ((double)p.alpha * tckd + (double)p.beta * nckd);
+    if (threadIdx.x == 0) { row_acc[i] = l; if (row_loss) row_loss[i] = (float)l; }
+    if (d) {
+        const double gs = grad_scale * inv_n, a = (double)p.alpha, b = (double)p.beta, sum_t = pt_g + pt_o;
+        for (int c = threadIdx.x; c < C; c += KD_THREADS) {
+            double v;
+            if (c == g) {
+                v = a * (ps_g * sum_t - pt_g);
+            } else {
+                const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
+                const double qs = exp(zs - mxs_n - lss_n), qt = exp(zt - mxt_n - lst_n);
+                v = a * (exp(zs - mxs - lss) * sum_t - pt_o * qs) + b * (qs * sqt - qt);
+            }
+            d[c] = dead ? NAN : (float)(gs * v);
+        }
+    }
+}
+
+// loss = sum of the row losses / n, summed in row order by one thread
+__global__ void kd_mean_kernel(const double* __restrict__ row_acc, int n, float* __restrict__ loss) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s += row_acc[i];
+    loss[0] = (float)(s / n);
+}
+
+rlcf_kd_params kd_default_params(void) {
+    rlcf_kd_params p;
+    p.T_stu = 1.f; p.T_tea = 1.f;                       // kd_distill_loss_v2
+    p.alpha = 1.f; p.beta = 0.5f; p.temperature = 1.f;  // dkd_distill_loss
+    p.multiplier = 2.f; p.eps = 1e-5f;                  // atkd_distill_loss
+    return p;
+}
+
+int launch_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, int mode, const int32_t* target,
+                   const rlcf_kd_params* params, float* loss, float* row_loss, float* dlogits, double* row_acc, hipStream_t st) {
+    RLCF_ARG_CHECK(student && teacher && row_acc && (loss || row_loss || dlogits));
+    if (mode != RLCF_KD_KD && mode != RLCF_KD_DKD && mode != RLCF_KD_ATKD) {
+        rlcf_set_error("kd_loss: mode %d is not RLCF_KD_KD / RLCF_KD_DKD / RLCF_KD_ATKD", mode);
+        return RLCF_ERR_ARG;
+    }
+    if (n <= 0 || C <= 0 || C > RLCF_KD_MAX_CLASSES) {
+        rlcf_set_error("kd_loss: n = %d rows of C = %d classes (need n >= 1, 1 <= C <= %d)", n, C, RLCF_KD_MAX_CLASSES);
+        return RLCF_ERR_ARG;
+    }
+    RLCF_ARG_CHECK(ld_s >= C && ld_t >= C);
+    const rlcf_kd_params p = params ? *params : kd_default_params();
+    if (mode == RLCF_KD_KD) RLCF_ARG_CHECK(p.T_stu > 0.f && p.T_tea > 0.f);
+    if (mode == RLCF_KD_DKD) RLCF_ARG_CHECK(p.temperature > 0.f);
+    kd_rows_kernel<<<dim3(n), dim3(KD_THREADS), 0, st>>>(student, ld_s, teacher, ld_t, C, mode, target, p, 1.0 / n, row_acc, row_loss, dlogits);
+    RLCF_LAUNCH_CHECK();
+    if (loss) {
+        kd_mean_kernel<<<dim3(1), dim3(64), 0, st>>>(row_acc, n, loss);
+        RLCF_LAUNCH_CHECK();
+    }
+    return RLCF_OK;
+}

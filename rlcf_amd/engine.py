@@ -32,6 +32,19 @@ def _cfg(g: ClipGeometry) -> L.ClipCfg:
                      g.context_length, g.vocab_size, g.transformer_width, g.transformer_heads, g.transformer_layers)
 
 
+KD_FLAGS = {"KD": L.F_KD, "DKD": L.F_DKD, "ATKD": L.F_ATKD}
+KD_MODES = {"KD": L.KD_KD, "DKD": L.KD_DKD, "ATKD": L.KD_ATKD}
+
+
+def kd_flag(kd_loss: Optional[str]) -> int:
+    """the loss-kind field of rlcf_tta_args.flags for `--kd_loss` (tune_cls_kd.py:48-55 raise on anything else)"""
+    if kd_loss is None:
+        return 0
+    if kd_loss not in KD_FLAGS:
+        raise NotImplementedError(f"kd_loss {kd_loss!r}: one of {sorted(KD_FLAGS)}")
+    return KD_FLAGS[kd_loss]
+
+
 @dataclass
 class TTAConfig:
     """Flags read on the path (reference TPT/params.py:13-98; script values TPT/scripts/rlcf-prompt.sh)."""
@@ -50,10 +63,12 @@ class TTAConfig:
     min_entropy_reg: bool = False
     min_entropy_w: float = 0.1           # TPT/params.py:66
     sparse_backward: bool = True
+    kd_loss: Optional[str] = None        # --kd_loss of TPT/tune_cls_kd.py: "KD" / "DKD" / "ATKD" replace the reward loss (None = RL)
 
     def flags(self) -> int:
         return ((L.F_REWARD_PROCESS if self.reward_process else 0) | (L.F_AMPLIFY if self.reward_amplify else 0) |
-                (L.F_PROCESS_BATCH if self.process_batch else 0) | (L.F_MIN_ENTROPY if self.min_entropy_reg else 0))
+                (L.F_PROCESS_BATCH if self.process_batch else 0) | (L.F_MIN_ENTROPY if self.min_entropy_reg else 0) |
+                kd_flag(self.kd_loss))
 
     def n_sel(self, n_views: int) -> int:
         """int(N * top) of select_confident_samples (TPT/tpt_cls_rl.py:34): Python's double product, truncated."""
@@ -65,6 +80,25 @@ class TTAConfig:
                          self.beta2, self.eps, self.flags(), self.clipscore_weight, self.min_entropy_w,
                          1 if self.sparse_backward else 0, 1 if skip_final else 0,
                          ctx_in.data_ptr() if ctx_in is not None else None, self.n_sel(n_views))
+
+
+def kd_loss_op(student: torch.Tensor, teacher: torch.Tensor, mode: int, target: Optional[torch.Tensor] = None,
+               params: Optional[L.KdParams] = None, row_loss: bool = False):
+    """One rlcf_kd_loss launch on float32 device rows (any row stride): (loss [1], dlogits [n, C], per-row losses [n] or None)."""
+    assert student.dim() == 2 and student.shape == teacher.shape and student.dtype == teacher.dtype == torch.float32
+    assert student.stride(1) == 1 and teacher.stride(1) == 1, "rows must be contiguous"
+    n, Cn = student.shape
+    dev = student.device
+    loss = torch.empty(1, device=dev)
+    dlogits = torch.empty(n, Cn, device=dev)
+    rows = torch.empty(n, device=dev) if row_loss else None
+    tg = None
+    if target is not None:
+        tg = target.to(dev, torch.int32).contiguous()
+    lib = L.lib()
+    L.check(lib.rlcf_kd_loss(student.data_ptr(), student.stride(0), teacher.data_ptr(), teacher.stride(0), n, Cn, int(mode), _ptr(tg),
+                             C.byref(params) if params is not None else None, _ptr(loss), _ptr(rows), _ptr(dlogits), _stream()), "kd_loss")
+    return loss, dlogits, rows
 
 
 class Engine:
@@ -237,6 +271,21 @@ class Engine:
         L.check(self.lib.rlcf_engine_reset_visual_state(self.h, _stream()), "reset_visual_state")
         self.reset_moved = False
 
+    def _kd_outputs(self, o: Dict[str, torch.Tensor], cfg: TTAConfig, n_sel: int) -> None:
+        """a distillation-loss call samples no classes (topk_idx / clip_score / rewards stay unwritten, so they are not returned);
+        it returns the first step's dlogits and the reward features of the selected views, the teacher's input"""
+        if not cfg.kd_loss:
+            return
+        for k in ("topk_idx", "clip_score", "rewards"):
+            o.pop(k, None)
+        o["dlogits"] = torch.empty(n_sel, self.n_cls, device=self.device)
+        o["reward_image_features"] = torch.empty(n_sel, self.reward.embed_dim, device=self.device)
+
+    def kd_loss(self, student: torch.Tensor, teacher: torch.Tensor, kind: str = "KD", target: Optional[torch.Tensor] = None,
+                params: Optional[L.KdParams] = None, row_loss: bool = False):
+        """rlcf_kd_loss: (loss [1], dlogits [n, C], row losses [n] or None) of one distillation loss (include/rlcf_hip.h)"""
+        return kd_loss_op(student, teacher, KD_MODES[kind], target, params, row_loss)
+
     def tta_sample_ln(self, views: torch.Tensor, cfg: TTAConfig, skip_final: bool = False) -> Dict[str, torch.Tensor]:
         """LayerNorm-tuning step (reference TPT/tune_cls_rl.py with CLIPCLS_TTA(only_norm=True))."""
         views = views.to(self.device, torch.float32).contiguous()
@@ -250,6 +299,7 @@ class Engine:
                  logits=torch.empty(N, Cn, device=dev), selected_idx=torch.empty(n_sel, dtype=torch.int32, device=dev),
                  topk_idx=torch.empty(n_sel, K, dtype=torch.int32, device=dev), clip_score=torch.empty(n_sel * K, device=dev),
                  rewards=torch.empty(n_sel * K, device=dev), loss=torch.empty(1, device=dev))
+        self._kd_outputs(o, cfg, n_sel)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(N, skip_final)
         L.check(self.lib.rlcf_tta_sample_ln(self.h, _ptr(views), N, C.byref(a), C.byref(co), _stream()), "tta_sample_ln")
@@ -401,6 +451,7 @@ class Engine:
                  logits=torch.empty(N, Cn, device=dev), selected_idx=torch.empty(n_sel, dtype=torch.int32, device=dev),
                  topk_idx=torch.empty(n_sel, K, dtype=torch.int32, device=dev), clip_score=torch.empty(n_sel * K, device=dev),
                  rewards=torch.empty(n_sel * K, device=dev), loss=torch.empty(1, device=dev))
+        self._kd_outputs(o, cfg, n_sel)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(N, skip_final)
         fn = self.lib.rlcf_tta_retrieval_image if retrieval else self.lib.rlcf_tta_sample_visual

@@ -1,6 +1,8 @@
 """Flags of the RLCF classification entry points: same names, types and defaults as the reference (TPT/params.py:13-98), so the command
 lines of TPT/scripts/*.sh parse identically.  Flags the HIP path has no use for (--workers, --dataset_mode, --cocoop, --corruption,
---level, --kd_loss, --confidence_gap*) are accepted and ignored; --hard_aug 1 selects the BYOL-style recipe of the view pipeline (datautils.HardAugParams)."""
+--level, --confidence_gap*) are accepted and ignored; --hard_aug 1 selects the BYOL-style recipe of the view pipeline (datautils.HardAugParams);
+--kd_loss (KD / DKD / ATKD) is read by the distillation entry rlcf_amd.tune_cls_kd (TPT/tune_cls_kd.py, scripts/kd-tune.sh) and by
+nothing else."""
 import argparse
 
 

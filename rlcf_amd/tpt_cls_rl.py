@@ -55,10 +55,12 @@ def _config(args, optimizer, reward_model) -> TTAConfig:
                      min_entropy_w=float(getattr(args, "min_entropy_w", 0.1)))
 
 
-def test_time_tuning(model, inputs, optimizer, scaler, args, reward_model=None):
+def test_time_tuning(model, inputs, optimizer, scaler, args, reward_model=None, kd_loss=None):
     """TPT/tpt_cls_rl.py:47-79.  `optimizer` supplies the AdamW hyper-parameters (its state is reset per
     sample by the harness, :255, so the fused step starts from step 1); `scaler` is accepted and unused:
-    the HIP path computes in f32-grade precision, there is no loss scaling to apply."""
+    the HIP path computes in f32-grade precision, there is no loss scaling to apply.
+    kd_loss ("KD" / "DKD" / "ATKD", not in the reference's signature): the distillation loss of TPT/tune_cls_kd.py:34-61 in place of
+    the reward loss (rlcf_amd.tune_cls_kd passes it; the `--kd_loss` flag itself is read by that entry point only)."""
     # the tensor test_time_adapt_eval will pass to model(image) next (row 0 of `inputs`): consumed HERE, whatever happens below — an early
     # return or an exception must not leave it behind for an unrelated later call
     hint = getattr(model, "_clean_view_hint", None)
@@ -68,6 +70,10 @@ def test_time_tuning(model, inputs, optimizer, scaler, args, reward_model=None):
     if args.tta_steps <= 0:
         return
     cfg = _config(args, optimizer, reward_model)
+    if kd_loss is not None:
+        if hasattr(model, "prompt_learner"):
+            raise NotImplementedError("the distillation losses tune the image encoder (CLIPCLS_TTA); tune_cls_kd.py has no prompt form")
+        cfg.kd_loss = kd_loss
     eng = runtime.SESSION.engine(inputs.shape[0])
     if not hasattr(model, "prompt_learner"):               # CLIPCLS_TTA: image-encoder tuning (TPT/tune_cls_rl.py:31,217)
         full = not model.only_norm
@@ -279,14 +285,18 @@ def _loop_option(value, args, name):
     return value
 
 
-def test_time_adapt_eval(val_loader, model, optimizer, optim_state, scaler, args, device=None, reward_model=None, images_per_pass=None, in_flight=None):
+def test_time_adapt_eval(val_loader, model, optimizer, optim_state, scaler, args, device=None, reward_model=None, images_per_pass=None, in_flight=None,
+                         kd_loss=None):
     """TPT/tpt_cls_rl.py:219-279 and its twin TPT/tune_cls_rl.py:183-256 (CLIPCLS_TTA models: model.train() / model.eval() round the
     tuning step, :216-218, and model.momentum_update_model() after the clean-view inference, :240): per test image
     reset -> tune -> clean-view inference -> (EMA) -> top-1/top-5.
     `images_per_pass > 1` (not in the reference) hands that many test images to the engine at once; `in_flight > 1` (not in the reference
     either) keeps one image per engine call and runs that many samples side by side on their own engines and streams (_eval_in_flight).
-    Both need independent samples: no cross-sample EMA, no per-sample encoder weights."""
+    Both need independent samples: no cross-sample EMA, no per-sample encoder weights.
+    kd_loss: the loop of TPT/tune_cls_kd.py:191-236 (the same body, the tuning step distilling instead; one image per call)."""
     images_per_pass, in_flight = _loop_option(images_per_pass, args, "images_per_pass"), _loop_option(in_flight, args, "in_flight")
+    if kd_loss is not None and (images_per_pass > 1 or in_flight > 1):
+        raise NotImplementedError("the distillation losses run one test image per engine call (images_per_pass = in_flight = 1)")
     backbone = not hasattr(model, "prompt_learner")                 # CLIPCLS_TTA: the tune_cls_rl.py form of the loop
     full_visual = not hasattr(model, "prompt_learner") and not model.only_norm      # per-sample weights: one sample per pass
     if images_per_pass > 1 and args.tta_steps > 0 and not getattr(model, "momentum_update", False) and not full_visual:
@@ -331,7 +341,7 @@ def test_time_adapt_eval(val_loader, model, optimizer, optim_state, scaler, args
             model.train()                                           # tune_cls_rl.py:216
         elif args.tpt and image is not images and image.dim() == 4 and image.size(0) == 1:
             model._clean_view_hint = image                          # images = cat([image, views...]): row 0 of the step's input IS this tensor
-        test_time_tuning(model, images, optimizer, scaler, args, reward_model=reward_model)
+        test_time_tuning(model, images, optimizer, scaler, args, reward_model=reward_model, kd_loss=kd_loss)
         if backbone:
             model.eval()                                            # tune_cls_rl.py:218
         with torch.no_grad():
