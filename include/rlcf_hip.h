@@ -239,6 +239,24 @@ enum { RLCF_KD_KD = 1, RLCF_KD_DKD = 2, RLCF_KD_ATKD = 3, RLCF_KD_MAX_CLASSES = 
 typedef struct { float T_stu, T_tea, alpha, beta, temperature, multiplier, eps; } rlcf_kd_params;
 int rlcf_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, int mode, const int32_t* target,
                  const rlcf_kd_params* params, float* loss, float* row_loss, float* dlogits, rlcf_stream stream);
+/* (ABI version 16) Split-row form of RLCF_KD_KD for few, long rows — one retrieval query is ONE row of 5 000 (images) or 25 010
+ * (captions) logits (retrieval/clip_ret_kd.py:62,87).  A row is cut into chunks of 1024 elements that run on different workgroups:
+ * pass A reduces every chunk to (max, sum of exponentials) in double, pass B folds a row's chunk partials in chunk order, writes
+ * dlogits and partial losses, a last launch sums the partials in fixed order.  No atomics; the partition depends on C alone, so two
+ * calls, and two devices, give the same bits; floats are the double values rounded once.  Arguments as rlcf_kd_loss (KD only: T_stu,
+ * T_tea read; params NULL = 1, 1); 1 <= n <= RLCF_KD_SPLIT_MAX_ROWS (the rows are one grid dimension).  rlcf_kd_loss itself keeps
+ * the one-workgroup-per-row kernel for every call. */
+enum { RLCF_KD_SPLIT_MAX_ROWS = 65535 };
+int rlcf_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params,
+                       float* loss, float* row_loss, float* dlogits, rlcf_stream stream);
+/* (ABI version 16) Recall ranks of LAVIS RetrievalTask._report_metrics: ranks[r] = the number of columns of score row r (scores
+ * [rows, cols], row stride ld) that score STRICTLY higher than the best-scoring ground-truth column of that row.  gt_offsets != NULL:
+ * CSR, row r owns gt_indices[gt_offsets[r] .. gt_offsets[r + 1]) (image -> text, several captions per image); gt_offsets == NULL:
+ * gt_indices[r] alone (text -> image).  The reference ranks with np.argsort(...)[::-1], whose order among exactly equal scores is
+ * unspecified: here a column that ties with the ground-truth score does not outrank it.  A row without ground truth, or with an
+ * index outside [0, cols), gets -1.  All device pointers. */
+int rlcf_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_offsets, const int32_t* gt_indices,
+                         int32_t* ranks, rlcf_stream stream);
 
 /* torch.optim.AdamW single step (amsgrad off), TPT/tpt_cls_rl.py:78,120. step is 1-based. */
 int rlcf_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, int step,
@@ -513,6 +531,23 @@ int rlcf_tta_retrieval_image(rlcf_engine*, const float* images, int n, const rlc
 int rlcf_engine_set_image_bank(rlcf_engine*, const float* student_feats, const float* reward_feats, int n, rlcf_stream stream);
 int rlcf_tta_retrieval_text(rlcf_engine*, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_tta_out* out,
                             rlcf_stream stream);
+/* (ABI version 16) The distillation ablation of retrieval (retrieval/clip_ret_kd.py:50-92): the two calls above with the reward loss
+ * replaced by kd_distill_loss_v2(student logits, teacher logits, T_stu, T_tea) over ALL rows of the query's logits — no top-K, no
+ * CLIPScore, no reward processing.  The teacher rows are CLIPRewards.calulate_similarity (retrieval/clip_reward.py:218-227), computed
+ * ONCE before the steps:
+ *   image -> text:  exp(reward.logit_scale) * reward_image_features [n, Dr] @ reward caption bank^T   -> [n, C]
+ *   text -> image:  exp(reward.logit_scale) * reward_text_feature [1, Dr] @ reward image bank^T       -> [1, n_images]
+ * kd: only T_stu, T_tea are read (NULL = 1, 1).  args: sample_k, clipscore_weight and the reward-processing flags are ignored;
+ * RLCF_F_MIN_ENTROPY, RLCF_F_DKD and RLCF_F_ATKD are refused (the reference has no such form), and so is an engine with more than one
+ * reward model (CLIPRewardsMultiple has no calulate_similarity).  Outputs as the policy calls fill them — logits, loss, dlogits
+ * (dense: [n, C] / [n_images]), the gradient and "after" vectors, final_logits, step_skipped; topk_idx, clip_score and rewards stay
+ * unwritten.  The loss runs on rlcf_kd_loss_split's kernels for banks of 2048 rows and more, on rlcf_kd_loss's below (a function of
+ * the shape alone).  rlcf_engine_get_kd_teacher copies the teacher rows [n_rows, C] of the last distillation call out. */
+int rlcf_tta_retrieval_image_kd(rlcf_engine*, const float* images, int n, const rlcf_tta_args* args, const rlcf_kd_params* kd,
+                                const rlcf_tta_out* out, rlcf_stream stream);
+int rlcf_tta_retrieval_text_kd(rlcf_engine*, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_kd_params* kd,
+                               const rlcf_tta_out* out, rlcf_stream stream);
+int rlcf_engine_get_kd_teacher(rlcf_engine*, float* out, int n_rows, rlcf_stream stream);
 /* floats in the flat text vector (padding included; 0 + error on failure); *ln_count (optional) = floats of the LayerNorm vector */
 int64_t rlcf_engine_text_param_count(rlcf_engine*, int* ln_count, rlcf_stream stream);
 /* offsets / element counts of its 3 + 8*layers + 1 tensors in the order above; returns the number of tensors (or a negative error) */

@@ -94,6 +94,8 @@ SIGNATURES = {
     "rlcf_entropy_select": (I, [P, I, I, I, P, P, P]),
     "rlcf_reward_loss": (I, [P, I, P, I, I, I, P, P, I, F, I, F, P, P, P, P, P, P]),
     "rlcf_kd_loss": (I, [P, I, P, I, I, I, I, P, C.POINTER(KdParams), P, P, P, P]),
+    "rlcf_kd_loss_split": (I, [P, I, P, I, I, I, C.POINTER(KdParams), P, P, P, P]),
+    "rlcf_retrieval_ranks": (I, [P, I, I, I, P, P, P, P]),
     "rlcf_adamw_step": (I, [P, P, P, P, I64, I, F, F, F, F, F, P]),
     "rlcf_engine_create": (P, [C.POINTER(ClipCfg), C.POINTER(ClipCfg), I, I, I]),
     "rlcf_engine_destroy": (None, [P]),
@@ -126,6 +128,9 @@ SIGNATURES = {
     "rlcf_tta_sample_visual": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
     "rlcf_engine_set_image_bank": (I, [P, P, P, I, P]),
     "rlcf_tta_retrieval_text": (I, [P, P, P, P, P]),
+    "rlcf_tta_retrieval_image_kd": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(KdParams), C.POINTER(TTAOut), P]),
+    "rlcf_tta_retrieval_text_kd": (I, [P, P, C.POINTER(TTAArgs), C.POINTER(KdParams), C.POINTER(TTAOut), P]),
+    "rlcf_engine_get_kd_teacher": (I, [P, P, I, P]),
     "rlcf_engine_text_param_count": (I64, [P, P, P]),
     "rlcf_engine_text_param_layout": (I, [P, P, P, I, P]),
     "rlcf_engine_get_text_params": (I, [P, P, P, I, P]),

@@ -6,18 +6,22 @@ engine per query:
                                        (rlcf_engine_set_class_bank, n_ctx = 0); the image encoder is tuned;
   text -> image  (only_visual=False): rlcf_tta_retrieval_text over an image bank (rlcf_engine_set_image_bank); every non-visual
                                        parameter (embeddings, text transformer, ln_final, text_projection, logit_scale) is tuned.
-`text2image_loss` is the loss section of tune_text alone (rlcf_reward_loss with the two banks exchanged)."""
+`text2image_loss` is the loss section of tune_text alone (rlcf_reward_loss with the two banks exchanged).
+`test_time_tune` (clip_ret_policy.py:140-195) is the loop over the queries both retrieval entries share, `report_metrics` the
+recall@1/5/10 report of LAVIS's RetrievalTask._report_metrics on the rlcf_retrieval_ranks kernel."""
 from __future__ import annotations
 
+import os
 from typing import List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import clip_reward as _cr
 from . import clip_store, runtime
-from .engine import TTAConfig
+from .engine import TTAConfig, retrieval_ranks
 
 _VERSION = [0]       # bumped whenever a model or a reward model takes new image features (tune_text re-sends the bank to the engine then)
 
@@ -308,3 +312,78 @@ def text2image_loss(logits_per_text, reward_model, sample_k=None):
                                      flags, 0.0, o["topk_idx"].data_ptr(), o["clip_score"].data_ptr(), o["rewards"].data_ptr(),
                                      o["loss"].data_ptr(), o["dlogits"].data_ptr(), torch.cuda.current_stream().cuda_stream), "reward_loss")
     return o
+
+
+def _test_time_tune(tune_image_fn, tune_text_fn, data_loader, model, reward_model, scaler, optimizer, optim_state, text_bs, args):
+    """The loop retrieval/clip_ret_policy.py:140-195 and retrieval/clip_ret_kd.py:95-150 share: set the banks, then per query
+    tune -> score with the tuned model into one row of the score matrix -> momentum_update_model -> reset_initial -> optimizer state
+    reset.  The matrix of the other direction stays at -100."""
+    dev = model.device
+    ds = data_loader.dataset
+    score_i2t = torch.full((len(ds.image), len(ds.text)), -100.0, device=dev)
+    score_t2i = torch.full((len(ds.text), len(ds.image)), -100.0, device=dev)
+    _ = [os.path.join(ds.vis_root, f) for f in ds.image]                  # (image_filenames of the reference: built, unused)
+    texts = list(ds.text)
+
+    def restore():
+        if optimizer is not None and optim_state is not None and hasattr(optimizer, "load_state_dict"):
+            optimizer.load_state_dict(optim_state)
+
+    if model.only_visual:
+        model.set_text_bank(texts)                                        # tokenize_all_text + get_all_text_embeds + set_text_features
+        reward_model.set_many_text_features(texts, text_bs=text_bs)
+        for i, samples in enumerate(data_loader):
+            image = samples["image"].to(dev)
+            tune_image_fn(image, model, reward_model, optimizer, scaler, args=args)
+            logits_per_image, _ = model(image)
+            score_i2t[i] = logits_per_image[0]                            # (row = the loader index, first image of the item: :128)
+            model.momentum_update_model()
+            model.reset_initial()
+            restore()
+    else:
+        model.set_image_features(image_features=torch.cat([model.get_image_features(s["image"].to(dev)) for s in data_loader], dim=0))
+        reward_model.set_image_features_with_dataloder(data_loader)
+        for i, text in enumerate(texts):
+            tune_text_fn(text, model, reward_model, optimizer, scaler, args=args)
+            _, logits_per_text = model(images=None, text=text)
+            score_t2i[i] = logits_per_text[0]
+            model.momentum_update_model()
+            model.reset_initial()
+            restore()
+    return score_i2t.detach().cpu().numpy(), score_t2i.detach().cpu().numpy()
+
+
+def test_time_tune(data_loader, device, model, reward_model=None, scaler=None, optimizer=None, optim_state=None, text_bs=128, args=None):
+    """retrieval/clip_ret_policy.py:140-195.  The loader is duck-typed: data_loader.dataset.image / .text / .vis_root, iteration yields
+    {"image": tensor}.  -> (score_matrix_i2t, score_matrix_t2i) as numpy arrays."""
+    return _test_time_tune(tune_image, tune_text, data_loader, model, reward_model, scaler, optimizer, optim_state, text_bs, args)
+
+
+test_time_tune.__test__ = False          # (the reference's name; not a test)
+
+
+def report_metrics(scores_i2t, scores_t2i, txt2img, img2txt):
+    """LAVIS RetrievalTask._report_metrics (lavis/tasks/retrieval.py:54-107) without the file it appends to: recall@1/5/10 of both
+    directions and their means, the ranks from the rlcf_retrieval_ranks kernel.  rank = the number of columns scoring strictly higher
+    than the best-scoring ground-truth column; the reference ranks with np.argsort(...)[::-1], whose order among exactly equal scores
+    is unspecified — a tie with the ground-truth score counts in its favour here.
+    img2txt: per image the list of its caption indices;  txt2img: per caption its image index."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_img = scores_i2t.shape[0]
+    per = [list(np.atleast_1d(np.asarray(img2txt[i])).tolist()) for i in range(n_img)]
+    off = torch.tensor(np.concatenate([[0], np.cumsum([len(p) for p in per])]), dtype=torch.int32)
+    idx = torch.tensor([int(j) for p in per for j in p], dtype=torch.int32)
+    r_i2t = retrieval_ranks(torch.as_tensor(np.asarray(scores_i2t), dtype=torch.float32).to(dev), idx, off).cpu().numpy()
+    t2i = torch.tensor([int(txt2img[i]) for i in range(scores_t2i.shape[0])], dtype=torch.int32)
+    r_t2i = retrieval_ranks(torch.as_tensor(np.asarray(scores_t2i), dtype=torch.float32).to(dev), t2i).cpu().numpy()
+    if (r_i2t < 0).any() or (r_t2i < 0).any():
+        raise ValueError("report_metrics: a row without ground truth, or a ground-truth index outside the score matrix")
+
+    def recall(r):
+        return [100.0 * int((r < k).sum()) / len(r) for k in (1, 5, 10)]
+
+    tr1, tr5, tr10 = recall(r_i2t)
+    ir1, ir5, ir10 = recall(r_t2i)
+    tr_mean, ir_mean = (tr1 + tr5 + tr10) / 3, (ir1 + ir5 + ir10) / 3
+    return {"txt_r1": tr1, "txt_r5": tr5, "txt_r10": tr10, "txt_r_mean": tr_mean, "img_r1": ir1, "img_r5": ir5, "img_r10": ir10,
+            "img_r_mean": ir_mean, "r_mean": (tr_mean + ir_mean) / 2, "agg_metrics": (tr1 + tr5 + tr10) / 3}

@@ -35,7 +35,7 @@ int rlcf_func_lds(const void* fn, size_t bytes) {
 extern "C" {
 
 const char* rlcf_last_error(void) { return g_err; }
-int rlcf_version(void) { return 15; }   // 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
+int rlcf_version(void) { return 16; }   // 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
 //    // 2: rlcf_clip_cfg.vision_stages, reward slots, views, LN batch; 3: rlcf_tta_out.vis_*, rlcf_tta_sample_visual
 
 // ------------------------------------------------------------------ op level
@@ -448,6 +448,26 @@ int rlcf_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t,
     (void)hipFreeAsync(acc, (hipStream_t)stream);
     return rc;
 }
+int rlcf_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params, float* loss,
+                       float* row_loss, float* dlogits, rlcf_stream stream) {
+    RLCF_ARG_CHECK(student && teacher && (loss || row_loss || dlogits));
+    if (n <= 0 || n > RLCF_KD_SPLIT_MAX_ROWS || C <= 0 || C > RLCF_KD_MAX_CLASSES) {
+        rlcf_set_error("kd_loss_split: n = %d rows of C = %d classes (need 1 <= n <= %d, 1 <= C <= %d)", n, C, RLCF_KD_SPLIT_MAX_ROWS,
+                       RLCF_KD_MAX_CLASSES);
+        return RLCF_ERR_ARG;
+    }
+    RLCF_ARG_CHECK(ld_s >= C && ld_t >= C);
+    if (params) RLCF_ARG_CHECK(params->T_stu > 0.f && params->T_tea > 0.f);
+    double* ws = nullptr;
+    RLCF_HIP_CHECK(hipMallocAsync((void**)&ws, kd_split_ws_bytes(n, C), (hipStream_t)stream));
+    const int rc = launch_kd_loss_split(student, ld_s, teacher, ld_t, n, C, params, loss, row_loss, dlogits, nullptr, ws, (hipStream_t)stream);
+    (void)hipFreeAsync(ws, (hipStream_t)stream);
+    return rc;
+}
+int rlcf_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_offsets, const int32_t* gt_indices, int32_t* ranks,
+                         rlcf_stream stream) {
+    return launch_retrieval_ranks(scores, ld, rows, cols, gt_offsets, gt_indices, ranks, (hipStream_t)stream);
+}
 // the distillation loss kinds exist only on the one-image image-encoder tuning calls (tune_cls_kd.py has no prompt, batched, lane
 // or retrieval form)
 static int kd_refused(const rlcf_tta_args* a, const char* entry) {
@@ -490,6 +510,26 @@ int rlcf_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens_host, const rl
     RLCF_ARG_CHECK(e && tokens_host && args);
     if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_text")) return rc_;
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream));
+}
+int rlcf_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_kd_params* kd,
+                                const rlcf_tta_out* out, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && images && args && n > 0);
+    return engine_tta_retrieval_image_kd(e, images, n, args, kd, out, engine_stream(e, stream));
+}
+int rlcf_tta_retrieval_text_kd(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_kd_params* kd,
+                               const rlcf_tta_out* out, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && tokens_host && args);
+    const rlcf_kd_params p = kd ? *kd : kd_default_params();
+    return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream), &p);
+}
+int rlcf_engine_get_kd_teacher(rlcf_engine* e, float* out, int n_rows, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && out && n_rows > 0);
+    if (e->C <= 0 || e->kd_teacher_C != e->C || n_rows > e->kd_teacher_rows) {
+        rlcf_set_error("get_kd_teacher: no teacher rows [%d, %d] held (run a distillation call on this bank first)", n_rows, e->C);
+        return RLCF_ERR_STATE;
+    }
+    RLCF_HIP_CHECK(hipMemcpyAsync(out, e->kd_teacher.p, (size_t)n_rows * e->C * sizeof(float), hipMemcpyDeviceToDevice, engine_stream(e, stream)));
+    return RLCF_OK;
 }
 int64_t rlcf_engine_text_param_count(rlcf_engine* e, int* ln_count, rlcf_stream stream) {
     if (!e || engine_text_enable(e, engine_stream(e, stream)) != RLCF_OK) return 0;

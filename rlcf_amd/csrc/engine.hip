@@ -1310,6 +1310,7 @@ int engine_set_class_bank(rlcf_engine* e, const int32_t* tokens, int C, int n_ct
     RLCF_ARG_CHECK(C > 0 && C <= e->max_classes && n_ctx >= 0 && n_ctx + 3 <= s.cfg.context_length && (n_ctx == 0 || ctx_init));
     RLCF_ARG_CHECK(text_mode >= RLCF_TEXT_DENSE && text_mode <= RLCF_TEXT_SHARED);
     e->text_mode = text_mode; e->n_ctx = n_ctx; e->C = C; e->image_bank = false;
+    e->kd_teacher_rows = 0;
     const int Wt = s.cfg.text_width, D = s.cfg.embed_dim;
     RLCF_ARG_CHECK((ctx_pos == nullptr) == (student_tokens == nullptr) && (!ctx_pos || n_ctx > 0));
     TRY(build_layout(e, s, e->lay[0], ctx_pos ? student_tokens : tokens, C, n_ctx, true, text_mode, st, ctx_pos));

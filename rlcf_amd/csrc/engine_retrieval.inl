@@ -86,19 +86,7 @@ __global__ void scale_by_exp_kernel(float* __restrict__ x, const float* __restri
     const float s = expf(*log_scale);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] *= s;
 }
-// out[0] = sum_i a[i] * b[i]  (one block, fixed reduction order)
-__global__ void dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += a[i] * b[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
+// (dot_kernel, out[0] = sum_i a[i] * b[i]: engine_tuning.inl, next to the distillation loss that also uses it)
 // embedding gradients of one packed text: x[r] = token_embedding[token[r]] + positional_embedding[pos[r]] (model.py:344-346), so
 // d positional_embedding[pos[r]] += dX[r], d token_embedding[token[r]] += dX[r].  One thread per column walks the rows in order:
 // repeated tokens accumulate in a fixed order, no atomics.
@@ -123,6 +111,7 @@ int engine_set_image_bank(rlcf_engine* e, const float* student_feats, const floa
     RLCF_ARG_CHECK(student_feats && reward_feats && n > 0 && n <= e->max_classes);
     const int D = s.cfg.embed_dim;
     e->C = n; e->image_bank = true; e->n_ctx = 0;
+    e->kd_teacher_rows = 0;
     e->sp_max_e = 0; e->sp_groups = 0; e->b_cap = 0;
     TRY(tta_scratch_ensure(e, n));
     TRY(e->txt0.ensure((size_t)n * D * sizeof(float)));
@@ -159,12 +148,21 @@ static int rebuild_E(ClipModel& m, TextLayout& L, hipStream_t st) {
 // two parameter buffers.  Then logits_per_text of the tuned encoder (clip_ret_policy.py:193-195) and the reset (:196).
 // Outputs (rlcf_tta_out): logits [n], topk_idx, clip_score, rewards, loss, dlogits [n] of the first step; vis_grad / vis_after = the flat
 // text buffer (rlcf_engine_text_param_layout), ln_grad / ln_after = the text LayerNorm buffer; final_logits [n]; step_skipped.
-int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
+//
+// kd != NULL (rlcf_tta_retrieval_text_kd, retrieval/clip_ret_kd.py:70-92): the reward loss is replaced by kd_distill_loss_v2 of
+// logits_per_text against the teacher row r_logits_per_text = exp(reward.logit_scale) * reward_text @ reward_image_bank^T, computed
+// once before the steps (CLIPRewards.calulate_similarity); sample_k, clipscore_weight and the reward-processing flags are not read and
+// topk_idx / clip_score / rewards stay unwritten.
+int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st,
+                              const rlcf_kd_params* kd) {
     ClipModel& s = e->model[RLCF_STUDENT];
+    if (kd) TRY(engine_kd_refusals(e, a, "rlcf_tta_retrieval_text_kd"));
     if (e->C <= 0 || !e->image_bank || e->n_rewards <= 0) { rlcf_set_error("image bank / reward model not set"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(tokens && a && a->tta_steps >= 0 && a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+    RLCF_ARG_CHECK(tokens && a && a->tta_steps >= 0);
+    if (kd) RLCF_ARG_CHECK(kd->T_stu > 0.f && kd->T_tea > 0.f);
+    else RLCF_ARG_CHECK(a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
     TRY(engine_text_enable(e, st));
-    const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, L = s.cfg.text_layers;
+    const int C = e->C, K = kd ? 1 : a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, L = s.cfg.text_layers;
     const rlcf_tta_out none{};
     if (!out) out = &none;
     e->last_flops = 0.0;
@@ -206,6 +204,7 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
     // reward_model.set_text_features(captions=text) (clip_ret_policy.py:117): the query under every reward model, frozen
     for (int m = 0; m < e->n_rewards; ++m)
         TRY(text_forward(e, e->model[RLCF_REWARD + m], e->qlay[1 + m], e->tt, nullptr, query_io(e->qlay[1 + m], e->rimg[m].as<float>()), false, st));
+    if (kd) TRY(kd_teacher(e, 1, st));
     const TextPassIO io = query_io(Q, e->q_feat.as<float>());
     float* const ls = e->tw.as<float>() + e->tw_slots.back().off;
     float* const G = e->tw_grad.as<float>();
@@ -219,14 +218,18 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
     for (int j = 0; j < a->tta_steps; ++j) {
         TRY(text_forward(e, s, Q, e->st, nullptr, io, true, st));
         TRY(logits_per_text(e->sel_logits.as<float>()));
-        TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, 1, C, K, reward_bank(e), a->clipscore_weight, a->flags,
-                                    a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(), e->rewards.as<float>(),
-                                    e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
+        if (!kd) TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, 1, C, K, reward_bank(e), a->clipscore_weight, a->flags,
+                                             a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(), e->rewards.as<float>(),
+                                             e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
         RLCF_HIP_CHECK(hipMemsetAsync(G, 0, wb, st));
         RLCF_HIP_CHECK(hipMemsetAsync(GL, 0, lb, st));
         // logits = exp(logit_scale) * <feat, bank>:  d logit_scale = <dlogits, logits>,  d feat = exp(logit_scale) * dlogits @ bank
-        dot_kernel<<<dim3(1), dim3(256), 0, st>>>(e->dlogits.as<float>(), e->sel_logits.as<float>(), C, G + e->tw_slots.back().off);
-        RLCF_LAUNCH_CHECK();
+        if (kd) {              // (the loss kernels hand the dot product over with the gradient row)
+            TRY(kd_retrieval_loss(e, e->sel_logits.as<float>(), 1, kd, G + e->tw_slots.back().off, st));
+        } else {
+            dot_kernel<<<dim3(1), dim3(256), 0, st>>>(e->dlogits.as<float>(), e->sel_logits.as<float>(), C, G + e->tw_slots.back().off);
+            RLCF_LAUNCH_CHECK();
+        }
         TRY(launch_dimg(e->dlogits.as<float>(), e->txt0.as<float>(), 1, C, D, 1.0f, e->q_dfeat.as<float>(), st));
         scale_by_exp_kernel<<<dim3(1), dim3(256), 0, st>>>(e->q_dfeat.as<float>(), ls, D);
         RLCF_LAUNCH_CHECK();
@@ -244,9 +247,11 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
         RLCF_LAUNCH_CHECK();
         if (j == 0) {
             COPY_OUT(out->logits, e->sel_logits.p, (size_t)C * sizeof(float));
-            COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)K * sizeof(int32_t));
-            COPY_OUT(out->clip_score, e->clip_score.p, (size_t)K * sizeof(float));
-            COPY_OUT(out->rewards, e->rewards.p, (size_t)K * sizeof(float));
+            if (!kd) {
+                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)K * sizeof(int32_t));
+                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)K * sizeof(float));
+                COPY_OUT(out->rewards, e->rewards.p, (size_t)K * sizeof(float));
+            }
             COPY_OUT(out->loss, e->loss.p, sizeof(float));
             COPY_OUT(out->dlogits, e->dlogits.p, (size_t)C * sizeof(float));
             COPY_OUT(out->vis_grad, G, wb);

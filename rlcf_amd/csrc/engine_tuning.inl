@@ -161,9 +161,10 @@ int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, co
 // The KD ablation adapts the same student with the same frozen CLIP, the reward loss replaced by a distillation loss against the
 // reward model's logits of the selected views; selection, backward, step skip and AdamW are the RL path's.
 static int kd_mode(const rlcf_tta_args* a) { return (a->flags & RLCF_F_KD_MASK) >> 5; }
-static int kd_check(const rlcf_engine* e, const rlcf_tta_args* a) {
+// retrieval: the caller is rlcf_tta_retrieval_image_kd, the one entry that distils over rows taken in order
+static int kd_check(const rlcf_engine* e, const rlcf_tta_args* a, bool retrieval = false) {
     if (!kd_mode(a)) return RLCF_OK;
-    if (a->flags & (RLCF_F_MIN_ENTROPY | RLCF_F_NO_SELECTION)) {
+    if (a->flags & (RLCF_F_MIN_ENTROPY | (retrieval ? 0 : RLCF_F_NO_SELECTION))) {
         rlcf_set_error("the distillation losses take no min-entropy regulariser and no retrieval rows (flags 0x%x)", a->flags);
         return RLCF_ERR_ARG;
     }
@@ -179,11 +180,48 @@ static int kd_teacher(rlcf_engine* e, int n_sel, hipStream_t st) {
     const ClipModel& r = e->model[RLCF_REWARD];
     const int Dr = r.cfg.embed_dim, C = e->C;
     TRY(e->kd_teacher.ensure((size_t)n_sel * C * sizeof(float)));
+    e->kd_teacher_rows = n_sel; e->kd_teacher_C = C;
     return gemm(e, e->rimg[0].as<float>(), Dr, e->reward_cls[0].as<float>(), Dr, nullptr, nullptr, 0, nullptr, 0, e->kd_teacher.as<float>(), C,
                 n_sel, C, Dr, r.logit_scale_exp, RLCF_EPI_NONE, st);
 }
 // loss and dlogits of one step (tune_cls_kd.py:48-55) into e->loss / e->dlogits, where the reward loss leaves them
-static int kd_step(rlcf_engine* e, int n_sel, const rlcf_tta_args* a, hipStream_t st) {
+// retrieval (retrieval/clip_ret_kd.py:62,87): kd_distill_loss_v2 over one or a few rows as long as the bank.  The split-row kernels
+// take over from the one-workgroup-per-row kernel where they are faster (profiles/retrieval_kd_notes.md); the choice depends on
+// (n, C) only, so a given query computes the same bits on every device.  dot (optional) = <dlogits, student>, one float.
+// out[0] = sum_i a[i] * b[i]  (one block, fixed reduction order)
+__global__ void dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out) {
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) acc += a[i] * b[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+static bool kd_split_wins(int n, int C) { return C >= KD_SPLIT_MIN_C; }
+static int kd_retrieval_loss(rlcf_engine* e, const float* student, int n, const rlcf_kd_params* kdp, float* dot, hipStream_t st) {
+    const int C = e->C;
+    if (kd_split_wins(n, C)) {
+        TRY(e->kd_ws.ensure(kd_split_ws_bytes(n, C)));
+        return launch_kd_loss_split(student, C, e->kd_teacher.as<float>(), C, n, C, kdp, e->loss.as<float>(), nullptr, e->dlogits.as<float>(),
+                                    dot, (double*)e->kd_ws.p, st);
+    }
+    TRY(e->kd_ws.ensure((size_t)n * sizeof(double)));
+    TRY(launch_kd_loss(student, C, e->kd_teacher.as<float>(), C, n, C, RLCF_KD_KD, nullptr, kdp, e->loss.as<float>(), nullptr,
+                       e->dlogits.as<float>(), (double*)e->kd_ws.p, st));
+    if (dot) {
+        RLCF_ARG_CHECK(n == 1);
+        dot_kernel<<<dim3(1), dim3(256), 0, st>>>(e->dlogits.as<float>(), student, C, dot);
+        RLCF_LAUNCH_CHECK();
+    }
+    return RLCF_OK;
+}
+// rkd != NULL: the retrieval form (rlcf_tta_retrieval_image_kd), kd_distill_loss_v2 with its temperatures over rows as long as the bank
+static int kd_step(rlcf_engine* e, int n_sel, const rlcf_tta_args* a, hipStream_t st, const rlcf_kd_params* rkd = nullptr) {
+    if (rkd) return kd_retrieval_loss(e, e->sel_logits.as<float>(), n_sel, rkd, nullptr, st);
     return launch_kd_loss(e->sel_logits.as<float>(), e->C, e->kd_teacher.as<float>(), e->C, n_sel, e->C, kd_mode(a), nullptr, nullptr,
                           e->loss.as<float>(), nullptr, e->dlogits.as<float>(), (double*)e->rl_stats.p, st);
 }
@@ -303,7 +341,8 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
     return RLCF_OK;
 }
 
-static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full);
+static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full,
+                               const rlcf_kd_params* rkd = nullptr);
 int engine_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
     return tta_sample_backbone(e, views, N, a, out, st, false);
 }
@@ -318,16 +357,19 @@ static int visual_reset(rlcf_engine* e, hipStream_t st) {      // visual.load_st
     e->vw_dirty = false;
     return engine_visual_refresh(e, st, e->vw_init_is_ckpt);
 }
-static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full) {
+// rkd != NULL: retrieval distillation (rlcf_tta_retrieval_image_kd): rows in order, KD with these temperatures on every row
+static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full,
+                               const rlcf_kd_params* rkd) {
     ClipModel& s = e->model[RLCF_STUDENT];
     if (e->C <= 0 || e->image_bank || e->n_rewards <= 0) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
     RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a && a->tta_steps >= 0 && a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
-    TRY(kd_check(e, a));
+    TRY(kd_check(e, a, rkd != nullptr));
     const bool kd = kd_mode(a) != 0;
     if (is_resnet(s.cfg)) {
+        if (rkd) { rlcf_set_error("retrieval distillation tunes a ViT image encoder (CLIPRet_TTA)"); return RLCF_ERR_ARG; }
         return engine_tta_sample_bn(e, views, N, a, out, st, full);
     }
     RLCF_ARG_CHECK(s.tokens <= 320);
@@ -364,7 +406,7 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
         }
         TRY(vit_forward_saved(e, s, e->views_sel.as<float>(), n_sel, e->ln_feat.as<float>(), st));
         TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
-        if (kd) TRY(kd_step(e, n_sel, a, st));
+        if (kd) TRY(kd_step(e, n_sel, a, st, rkd));
         else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
@@ -409,4 +451,36 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
     RLCF_HIP_CHECK(hipMemcpyAsync(e->ln_params.p, e->ln_init.p, nb, hipMemcpyDeviceToDevice, st));
     if (full) TRY(visual_reset(e, st));
     return RLCF_OK;
+}
+
+// ------------------------------------------------------------------ retrieval distillation (retrieval/clip_ret_kd.py)
+// what both retrieval KD entries refuse before anything is launched
+int engine_kd_refusals(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry) {
+    if (a->flags & RLCF_F_MIN_ENTROPY) {
+        rlcf_set_error("%s: the distillation losses take no min-entropy regulariser (flags 0x%x)", entry, a->flags);
+        return RLCF_ERR_ARG;
+    }
+    if (a->flags & RLCF_F_DKD) {       // (RLCF_F_DKD is the high bit of the field: set in RLCF_F_DKD and RLCF_F_ATKD, clear in RLCF_F_KD)
+        rlcf_set_error("%s: retrieval distils with kd_distill_loss_v2 only (retrieval/clip_ret_kd.py has no DKD / ATKD form)", entry);
+        return RLCF_ERR_ARG;
+    }
+    if (e->n_rewards != 1) {
+        rlcf_set_error("the distillation losses need exactly one reward model (the engine holds %d)", e->n_rewards);
+        return RLCF_ERR_ARG;
+    }
+    return RLCF_OK;
+}
+// image -> text (clip_ret_kd.py:50-67): every-parameter tuning of the image encoder over all n query rows against the caption bank,
+// teacher = kd_teacher() once before the steps, loss = KD over the dense rows [n, C]
+int engine_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* a, const rlcf_kd_params* kd,
+                                  const rlcf_tta_out* out, hipStream_t st) {
+    TRY(engine_kd_refusals(e, a, "rlcf_tta_retrieval_image_kd"));
+    if (e->C <= 0 || e->image_bank) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
+    const rlcf_kd_params p = kd ? *kd : kd_default_params();
+    RLCF_ARG_CHECK(p.T_stu > 0.f && p.T_tea > 0.f);
+    rlcf_tta_args b = *a;
+    b.selection_p = 1.0f; b.n_sel = n; b.sample_k = 1;
+    b.flags = RLCF_F_NO_SELECTION | RLCF_F_KD;          // no sampling, no CLIPScore, no reward processing on this path
+    TRY(engine_visual_enable(e, st));
+    return tta_sample_backbone(e, images, n, &b, out, st, true, &p);
 }

@@ -244,3 +244,207 @@ int launch_kd_loss(const float* student, int ld_s, const float* teacher, int ld_
     }
     return RLCF_OK;
 }
+
+// ------------------------------------------------------------------ split-row form of the KD loss (retrieval: few, long rows)
+// retrieval/clip_ret_kd.py:50-92 distils ONE query row of 5 000 (images) or 25 010 (captions) logits per step: one workgroup per row
+// leaves 255 of 256 CUs idle on the critical path of every tuning step.  Here a row is cut into chunks of KD_SPLIT_CHUNK elements
+// (a compile-time constant: the partition, and with it every bit of the result, is the same on every device) and the chunks run on
+// different workgroups, grid = (chunks, rows):
+//   pass A  each workgroup reduces its chunk of z_s = s / T_s and z_t = t / T_t to (max, sum of exp(z - max)), in double;
+//   pass B  every workgroup of a row folds the row's chunk partials in chunk order (the same arithmetic in each of them: one wave
+//           rescales the <= 64 partials, one thread adds them in order) into
+//           the row's maxima, log-sum-exps and sum(pt), writes dlogits of its chunk and its partial row loss, and the partial
+//           <dlogits, s> the text direction turns into d logit_scale (logits = exp(logit_scale) * <feat, bank>);
+//   final   one workgroup sums the partials per row in chunk order and the rows in row order.
+// No atomics, no cooperative launch, each element read into registers once per pass; float results are the double values rounded once.
+// Gradient as in the one-workgroup kernel: d/ds_c = T_s * (ps_c * sum(pt) - pt_c) / n, sum(pt) = sum over chunks of the chunk's
+// share st_k * exp(mt_k - mxt - lst) (kept literal; 1 to within rounding).
+#define KD_SPLIT_CHUNK 1024
+#define KD_SPLIT_PER (KD_SPLIT_CHUNK / KD_THREADS)
+#define KD_SPLIT_WS 8          // doubles of workspace per (row, chunk): A {ms, ss, mt, st}, B {loss, dot}
+static_assert(KD_SPLIT_CHUNK % KD_THREADS == 0, "a chunk is a whole number of elements per thread");
+static_assert(RLCF_KD_MAX_CLASSES <= 64 * KD_SPLIT_CHUNK, "pass B folds a row's chunk partials on the 64 lanes of one wave");
+
+int kd_split_chunks(int C) { return (C + KD_SPLIT_CHUNK - 1) / KD_SPLIT_CHUNK; }
+size_t kd_split_ws_bytes(int n, int C) { return ((size_t)n * kd_split_chunks(C) * KD_SPLIT_WS + (size_t)n) * sizeof(double); }
+
+__global__ __launch_bounds__(KD_THREADS) void kd_split_a_kernel(const float* __restrict__ stu, int ld_s, const float* __restrict__ tea, int ld_t,
+                                                                int C, double ks, double kt, double* __restrict__ ws) {
+    __shared__ double red[KD_THREADS / 64];
+    const int k = blockIdx.x, i = blockIdx.y, c0 = k * KD_SPLIT_CHUNK;
+    const float* x = stu + (size_t)i * ld_s;
+    const float* y = tea + (size_t)i * ld_t;
+    double zs[KD_SPLIT_PER], zt[KD_SPLIT_PER];
+    double ms = -INFINITY, mt = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < KD_SPLIT_PER; ++u) {
+        const int c = c0 + u * KD_THREADS + threadIdx.x;
+        const bool in = c < C;
+        zs[u] = in ? (double)x[c] * ks : -INFINITY;
+        zt[u] = in ? (double)y[c] * kt : -INFINITY;
+        ms = fmax(ms, zs[u]); mt = fmax(mt, zt[u]);
+    }
+    ms = kd_block_max(ms, red); mt = kd_block_max(mt, red);
+    double ss = 0.0, st = 0.0;
+#pragma unroll
+    for (int u = 0; u < KD_SPLIT_PER; ++u) {
+        const int c = c0 + u * KD_THREADS + threadIdx.x;
+        if (c < C) { ss += exp(zs[u] - ms); st += exp(zt[u] - mt); }
+    }
+    ss = kd_block_sum(ss, red); st = kd_block_sum(st, red);
+    if (threadIdx.x == 0) {
+        double* w = ws + ((size_t)i * gridDim.x + k) * KD_SPLIT_WS;
+        w[0] = ms; w[1] = ss; w[2] = mt; w[3] = st;
+    }
+}
+
+__global__ __launch_bounds__(KD_THREADS) void kd_split_b_kernel(const float* __restrict__ stu, int ld_s, const float* __restrict__ tea, int ld_t,
+                                                                int C, double ks, double kt, double gs, double* __restrict__ ws,
+                                                                float* __restrict__ dlogits) {
+    __shared__ double red[KD_THREADS / 64];
+    const int k = blockIdx.x, i = blockIdx.y, nch = gridDim.x, c0 = k * KD_SPLIT_CHUNK;
+    const float* x = stu + (size_t)i * ld_s;
+    const float* y = tea + (size_t)i * ld_t;
+    double* wrow = ws + (size_t)i * nch * KD_SPLIT_WS;
+    // the row's statistics from its chunk partials (identical arithmetic in every workgroup of the row): lane j of the first wave
+    // rescales chunk j's sums (one exp each, nch <= 64 lanes), thread 0 adds the terms in chunk order, LDS hands the results round
+    __shared__ double term_s[64], term_t[64], stat[5];
+    const int t = threadIdx.x;
+    double cms = -INFINITY, css = 0.0, cmt = -INFINITY, cst = 0.0, wmt = 0.0;
+    if (t < 64) {
+        if (t < nch) { cms = wrow[t * KD_SPLIT_WS]; css = wrow[t * KD_SPLIT_WS + 1]; cmt = wrow[t * KD_SPLIT_WS + 2]; cst = wrow[t * KD_SPLIT_WS + 3]; }
+        const double wms = kd_wave_max(cms);
+        wmt = kd_wave_max(cmt);
+        term_s[t] = t < nch ? css * exp(cms - wms) : 0.0;
+        term_t[t] = t < nch ? cst * exp(cmt - wmt) : 0.0;
+        if (t == 0) { stat[0] = wms; stat[1] = wmt; }
+    }
+    __syncthreads();
+    if (t == 0) {
+        double a = 0.0, b = 0.0;
+        for (int j = 0; j < nch; ++j) { a += term_s[j]; b += term_t[j]; }
+        stat[2] = log(a); stat[3] = log(b);
+    }
+    __syncthreads();
+    if (t < 64) term_t[t] = t < nch ? cst * exp(cmt - wmt - stat[3]) : 0.0;          // the chunk's share of sum(pt)
+    __syncthreads();
+    if (t == 0) {
+        double a = 0.0;
+        for (int j = 0; j < nch; ++j) a += term_t[j];
+        stat[4] = a;
+    }
+    __syncthreads();
+    const double mxs = stat[0], mxt = stat[1], lss = stat[2], lst = stat[3], spt = stat[4];
+    float* d = dlogits ? dlogits + (size_t)i * C : nullptr;
+    double l = 0.0, dot = 0.0;
+#pragma unroll
+    for (int u = 0; u < KD_SPLIT_PER; ++u) {
+        const int c = c0 + u * KD_THREADS + threadIdx.x;
+        if (c < C) {
+            const float xs = x[c];
+            const double lps = (double)xs * ks - mxs - lss, pt = exp((double)y[c] * kt - mxt - lst);
+            l += -pt * lps;
+            const float g = (float)(gs * (exp(lps) * spt - pt));
+            if (d) d[c] = g;
+            dot += (double)g * (double)xs;
+        }
+    }
+    l = kd_block_sum(l, red); dot = kd_block_sum(dot, red);
+    if (threadIdx.x == 0) { wrow[k * KD_SPLIT_WS + 4] = l; wrow[k * KD_SPLIT_WS + 5] = dot; }
+}
+
+// row i: loss_i = out_scale * sum_k partial (chunk order);  loss = sum_i loss_i / n (row order);  dot = sum_i sum_k <dlogits, s> partials
+__global__ __launch_bounds__(KD_THREADS) void kd_split_final_kernel(double* __restrict__ ws, int n, int nch, double out_scale,
+                                                                    float* __restrict__ loss, float* __restrict__ row_loss, float* __restrict__ dot) {
+    double* row_acc = ws + (size_t)n * nch * KD_SPLIT_WS;
+    __shared__ double sdot[KD_THREADS];
+    double dsum = 0.0;
+    for (int i = threadIdx.x; i < n; i += KD_THREADS) {
+        const double* w = ws + (size_t)i * nch * KD_SPLIT_WS;
+        double l = 0.0, dd = 0.0;
+        for (int k = 0; k < nch; ++k) { l += w[k * KD_SPLIT_WS + 4]; dd += w[k * KD_SPLIT_WS + 5]; }
+        l *= out_scale;
+        row_acc[i] = l;
+        if (row_loss) row_loss[i] = (float)l;
+        dsum += dd;
+    }
+    sdot[threadIdx.x] = dsum;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (loss) {
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) s += row_acc[i];
+        loss[0] = (float)(s / n);
+    }
+    if (dot) {
+        double s = 0.0;
+        for (int t = 0; t < KD_THREADS && t < n; ++t) s += sdot[t];
+        dot[0] = (float)s;
+    }
+}
+
+// KD only (RLCF_KD_KD).  ws: kd_split_ws_bytes(n, C) bytes.  dot (optional): sum_i <dlogits_i, student_i>, one float.
+int launch_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params, float* loss,
+                         float* row_loss, float* dlogits, float* dot, double* ws, hipStream_t st) {
+    RLCF_ARG_CHECK(student && teacher && ws && (loss || row_loss || dlogits || dot));
+    if (n <= 0 || n > RLCF_KD_SPLIT_MAX_ROWS || C <= 0 || C > RLCF_KD_MAX_CLASSES) {          // (rows are the grid's y dimension)
+        rlcf_set_error("kd_loss_split: n = %d rows of C = %d classes (need 1 <= n <= %d, 1 <= C <= %d)", n, C, RLCF_KD_SPLIT_MAX_ROWS,
+                       RLCF_KD_MAX_CLASSES);
+        return RLCF_ERR_ARG;
+    }
+    RLCF_ARG_CHECK(ld_s >= C && ld_t >= C);
+    const rlcf_kd_params p = params ? *params : kd_default_params();
+    RLCF_ARG_CHECK(p.T_stu > 0.f && p.T_tea > 0.f);
+    const double ks = 1.0 / (double)p.T_stu, kt = 1.0 / (double)p.T_tea, out_scale = (double)p.T_stu * (double)p.T_stu;
+    const int nch = kd_split_chunks(C);
+    const dim3 grid(nch, n);
+    kd_split_a_kernel<<<grid, dim3(KD_THREADS), 0, st>>>(student, ld_s, teacher, ld_t, C, ks, kt, ws);
+    RLCF_LAUNCH_CHECK();
+    kd_split_b_kernel<<<grid, dim3(KD_THREADS), 0, st>>>(student, ld_s, teacher, ld_t, C, ks, kt, out_scale * ks / n, ws, dlogits);
+    RLCF_LAUNCH_CHECK();
+    kd_split_final_kernel<<<dim3(1), dim3(KD_THREADS), 0, st>>>(ws, n, nch, out_scale, loss, row_loss, dot);
+    RLCF_LAUNCH_CHECK();
+    return RLCF_OK;
+}
+
+// ------------------------------------------------------------------ recall ranks (LAVIS RetrievalTask._report_metrics)
+// rank of a score row = the number of columns that score STRICTLY higher than the best-scoring ground-truth column; one workgroup
+// per row.  Ground truth: gt_off != NULL: CSR (row r owns gt_idx[gt_off[r] .. gt_off[r + 1])), image -> text;  gt_off == NULL: one
+// index per row, text -> image.  The reference ranks with np.argsort(...)[::-1], whose order among exactly equal scores is
+// unspecified: here a column that ties with the ground-truth score does not outrank it (ties count in its favour).
+// A row with no ground truth or an index outside [0, cols) gets rank -1.
+__global__ __launch_bounds__(KD_THREADS) void retrieval_ranks_kernel(const float* __restrict__ scores, int ld, int cols,
+                                                                     const int32_t* __restrict__ gt_off, const int32_t* __restrict__ gt_idx,
+                                                                     int32_t* __restrict__ ranks) {
+    __shared__ int redc[KD_THREADS / 64];
+    const int r = blockIdx.x;
+    const float* s = scores + (size_t)r * ld;
+    const int b = gt_off ? gt_off[r] : r, e = gt_off ? gt_off[r + 1] : r + 1;
+    bool ok = e > b;
+    float best = -INFINITY;
+    for (int j = b; j < e; ++j) {                     // a handful of captions per image: every thread walks them
+        const int g = gt_idx[j];
+        if (g < 0 || g >= cols) { ok = false; break; }
+        best = fmaxf(best, s[g]);
+    }
+    if (!ok) { if (threadIdx.x == 0) ranks[r] = -1; return; }
+    int cnt = 0;
+    for (int c = threadIdx.x; c < cols; c += KD_THREADS) cnt += s[c] > best ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < KD_THREADS / 64; ++w) t += redc[w];
+        ranks[r] = t;
+    }
+}
+
+int launch_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_off, const int32_t* gt_idx, int32_t* ranks,
+                           hipStream_t st) {
+    RLCF_ARG_CHECK(scores && gt_idx && ranks && rows > 0 && cols > 0 && ld >= cols);
+    retrieval_ranks_kernel<<<dim3(rows), dim3(KD_THREADS), 0, st>>>(scores, ld, cols, gt_off, gt_idx, ranks);
+    RLCF_LAUNCH_CHECK();
+    return RLCF_OK;
+}

@@ -140,6 +140,15 @@ int launch_topk_rows(const float* logits, int ld_logits, int rows, int C, int K,
 rlcf_kd_params kd_default_params(void);
 int launch_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, int mode, const int32_t* target,
                    const rlcf_kd_params* params, float* loss, float* row_loss, float* dlogits, double* row_acc, hipStream_t st);
+// split-row form of RLCF_KD_KD for few, long rows (retrieval): ws = caller-owned scratch of kd_split_ws_bytes(n, C) bytes;
+// dot (optional) = sum_i <dlogits_i, student_i>
+#define KD_SPLIT_MIN_C 2048       // the retrieval entries take the split kernels from this bank size on (profiles/retrieval_kd_notes.md)
+size_t kd_split_ws_bytes(int n, int C);
+int launch_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params, float* loss,
+                         float* row_loss, float* dlogits, float* dot, double* ws, hipStream_t st);
+// recall ranks of score rows (kd.hip): gt_off = CSR offsets [rows + 1] or NULL (one ground-truth index per row)
+int launch_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_off, const int32_t* gt_idx, int32_t* ranks,
+                           hipStream_t st);
 int launch_reward_loss_bank(const float* logits, int ld_logits, const int32_t* sel, int groups, int n_sel, int C, int K,
                             const RewardBank& bank, float clipscore_weight, int flags, float min_entropy_w, int32_t* topk_idx,
                             float* clip_score, float* rewards, float* loss, float* dlogits, float* stats, hipStream_t st);

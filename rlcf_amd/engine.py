@@ -101,6 +101,36 @@ def kd_loss_op(student: torch.Tensor, teacher: torch.Tensor, mode: int, target: 
     return loss, dlogits, rows
 
 
+def kd_loss_split_op(student: torch.Tensor, teacher: torch.Tensor, params: Optional[L.KdParams] = None, row_loss: bool = False):
+    """One rlcf_kd_loss_split call (kd_distill_loss_v2 on few, long rows; any row stride): (loss [1], dlogits [n, C], row losses or None)."""
+    assert student.dim() == 2 and student.shape == teacher.shape and student.dtype == teacher.dtype == torch.float32
+    assert student.stride(1) == 1 and teacher.stride(1) == 1, "rows must be contiguous"
+    n, Cn = student.shape
+    dev = student.device
+    loss = torch.empty(1, device=dev)
+    dlogits = torch.empty(n, Cn, device=dev)
+    rows = torch.empty(n, device=dev) if row_loss else None
+    L.check(L.lib().rlcf_kd_loss_split(student.data_ptr(), student.stride(0), teacher.data_ptr(), teacher.stride(0), n, Cn,
+                                       C.byref(params) if params is not None else None, _ptr(loss), _ptr(rows), _ptr(dlogits), _stream()),
+            "kd_loss_split")
+    return loss, dlogits, rows
+
+
+def retrieval_ranks(scores: torch.Tensor, gt_indices: torch.Tensor, gt_offsets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rlcf_retrieval_ranks: per score row, the number of columns scoring strictly higher than its best ground-truth column
+    (gt_offsets: CSR offsets [rows + 1] over gt_indices, or None = one index per row) -> int32 [rows]."""
+    s = scores.float()
+    if s.stride(1) != 1:
+        s = s.contiguous()
+    rows, cols = s.shape
+    gi = gt_indices.to(s.device, torch.int32).contiguous()
+    go = None if gt_offsets is None else gt_offsets.to(s.device, torch.int32).contiguous()
+    assert (go.numel() == rows + 1 and int(go[-1]) == gi.numel() and int(go[0]) == 0) if go is not None else gi.numel() == rows
+    ranks = torch.empty(rows, dtype=torch.int32, device=s.device)
+    L.check(L.lib().rlcf_retrieval_ranks(s.data_ptr(), s.stride(0), rows, cols, _ptr(go), _ptr(gi), _ptr(ranks), _stream()), "retrieval_ranks")
+    return ranks
+
+
 class Engine:
     """One student CLIP (+ frozen reward CLIPs: one geometry, or a list of up to MAX_REWARDS for the ensemble of
     CLIPRewardsMultiple, slot m addressed as which = REWARD + m) resident on the current GPU."""
@@ -456,6 +486,65 @@ class Engine:
         a = cfg.c_args(N, skip_final)
         fn = self.lib.rlcf_tta_retrieval_image if retrieval else self.lib.rlcf_tta_sample_visual
         L.check(fn(self.h, _ptr(views), N, C.byref(a), C.byref(co), _stream()), "tta_retrieval_image" if retrieval else "tta_sample_visual")
+        return o
+
+    def kd_teacher(self, n_rows: int = 1) -> torch.Tensor:
+        """the teacher rows [n_rows, bank] of the last distillation call (rlcf_engine_get_kd_teacher)"""
+        t = torch.empty(n_rows, self.n_cls, device=self.device)
+        L.check(self.lib.rlcf_engine_get_kd_teacher(self.h, _ptr(t), n_rows, _stream()), "get_kd_teacher")
+        return t
+
+    def tta_retrieval_image_kd(self, images: torch.Tensor, cfg: TTAConfig, T_stu: float = 1.0, T_tea: float = 1.0,
+                               skip_final: bool = False) -> Dict[str, torch.Tensor]:
+        """Image -> text retrieval distillation step: tune_image of retrieval/clip_ret_kd.py:50-67 (+ the evaluation of its loop) over
+        the caption bank given to set_class_bank(n_ctx=0).  cfg supplies tta_steps and the AdamW hyper-parameters only."""
+        images = images.to(self.device, torch.float32).contiguous()
+        N, Cn = images.shape[0], self.n_cls
+        npar = int(self.lib.rlcf_engine_ln_param_count(self.h))
+        nvis = int(self.lib.rlcf_engine_visual_param_count(self.h, _stream()))
+        if nvis <= 0:
+            L.check(-1, "tta_retrieval_image_kd (visual_param_count)")
+        dev = self.device
+        o = dict(final_logits=torch.empty(1, Cn, device=dev), top5=torch.empty(5, dtype=torch.int32, device=dev),
+                 ln_after=torch.empty(npar, device=dev), ln_grad=torch.empty(npar, device=dev),
+                 vis_after=torch.empty(nvis, device=dev), vis_grad=torch.empty(nvis, device=dev),
+                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
+                 logits=torch.empty(N, Cn, device=dev), dlogits=torch.empty(N, Cn, device=dev), loss=torch.empty(1, device=dev),
+                 reward_image_features=torch.empty(N, self.reward.embed_dim, device=dev))
+        co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
+        a = cfg.c_args(N, skip_final)
+        a.flags &= ~(L.F_REWARD_PROCESS | L.F_AMPLIFY | L.F_PROCESS_BATCH)
+        kp = L.KdParams(float(T_stu), float(T_tea), 1.0, 0.5, 1.0, 2.0, 1e-5)
+        L.check(self.lib.rlcf_tta_retrieval_image_kd(self.h, _ptr(images), N, C.byref(a), C.byref(kp), C.byref(co), _stream()),
+                "tta_retrieval_image_kd")
+        if cfg.tta_steps > 0:
+            o["teacher"] = self.kd_teacher(N)
+        return o
+
+    def tta_retrieval_text_kd(self, tokens: torch.Tensor, cfg: TTAConfig, T_stu: float = 1.0, T_tea: float = 1.0,
+                              skip_final: bool = False) -> Dict[str, torch.Tensor]:
+        """Text -> image retrieval distillation step: tune_text of retrieval/clip_ret_kd.py:70-92 (+ the evaluation of its loop) for
+        ONE query caption over the image bank given to set_image_bank."""
+        tok = tokens.reshape(-1).to("cpu", torch.int32).contiguous()
+        assert tok.numel() == self.student.context_length
+        ln_count = C.c_int(0)
+        nflat = int(self.lib.rlcf_engine_text_param_count(self.h, C.byref(ln_count), _stream()))
+        if nflat <= 0:
+            L.check(-1, "tta_retrieval_text_kd (text_param_count)")
+        dev, n = self.device, self.n_cls
+        o = dict(final_logits=torch.empty(1, n, device=dev), logits=torch.empty(1, n, device=dev), dlogits=torch.empty(1, n, device=dev),
+                 ln_after=torch.empty(ln_count.value, device=dev), ln_grad=torch.empty(ln_count.value, device=dev),
+                 vis_after=torch.empty(nflat, device=dev), vis_grad=torch.empty(nflat, device=dev),
+                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
+                 reward_image_features=torch.empty(1, self.rewards[0].embed_dim, device=dev), loss=torch.empty(1, device=dev))
+        co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
+        a = cfg.c_args(1, skip_final)
+        a.flags &= ~(L.F_REWARD_PROCESS | L.F_AMPLIFY | L.F_PROCESS_BATCH)
+        kp = L.KdParams(float(T_stu), float(T_tea), 1.0, 0.5, 1.0, 2.0, 1e-5)
+        L.check(self.lib.rlcf_tta_retrieval_text_kd(self.h, tok.data_ptr(), C.byref(a), C.byref(kp), C.byref(co), _stream()),
+                "tta_retrieval_text_kd")
+        o["text_after"], o["text_grad"], o["reward_text_features"] = o.pop("vis_after"), o.pop("vis_grad"), o.pop("reward_image_features")
+        o["teacher"] = self.kd_teacher(1)
         return o
 
     # ---- text-encoder tuning (retrieval text -> image, CLIPRet_TTA only_visual=False, retrieval/custom_models.py:139-147)
