@@ -199,7 +199,16 @@ enum { RLCF_F_REWARD_PROCESS = 1, RLCF_F_AMPLIFY = 2, RLCF_F_PROCESS_BATCH = 4, 
        RLCF_F_NO_SELECTION = 16 /* image-encoder tuning calls: rows taken in order, no confidence selection (set by rlcf_tta_retrieval_image) */,
        /* (ABI version 15) the loss kind of an image-encoder tuning call, a 2-bit field: 0 = the RL reward loss above; otherwise the
         * distillation loss of TPT/tune_cls_kd.py:48-55 against the reward model's logits (rlcf_kd_loss, mode = field >> 5) */
-       RLCF_F_KD = 32, RLCF_F_DKD = 64, RLCF_F_ATKD = 96, RLCF_F_KD_MASK = 96 };
+       RLCF_F_KD = 32, RLCF_F_DKD = 64, RLCF_F_ATKD = 96, RLCF_F_KD_MASK = 96,
+       /* (ABI version 17) the TPT baseline (TPT/tpt_cls.py:49-72, TPT/tune_cls_tpt.py:34-54): loss = avg_entropy of the selected views
+        * (rlcf_tpt_loss) in place of the reward loss.  Accepted by rlcf_tta_sample, rlcf_tta_sample_ln, rlcf_tta_sample_visual (ViT and
+        * ModifiedResNet students), rlcf_tta_batch_ln (fused, one group per sample) and rlcf_tta_batch (sample by sample).  No reward
+        * model is needed (rlcf_engine_create(student, NULL, ...)); one that is held is not run: no reward pass, no teacher, no top-K
+        * stage, sample_k ignored, the prompt path takes the dense class backward.  out->topk_idx / clip_score / rewards /
+        * reward_image_features stay unwritten; loss, dlogits, the gradients and step_skipped are filled as before; tta_steps = 0 is
+        * plain inference.  Refused (RLCF_ERR_ARG) together with RLCF_F_KD_MASK, RLCF_F_MIN_ENTROPY or RLCF_F_NO_SELECTION, and by
+        * rlcf_tta_lanes, rlcf_lanes_submit and the four retrieval entries. */
+       RLCF_F_TPT = 128 };
 /* The loss section of test_time_tuning (TPT/tpt_cls_rl.py:63-74) with
  * CLIPRewards.CLIPScore / rewards_post_process (TPT/clip_reward.py:111-128,152-165):
  * rows = logits[sel[i]] (sel NULL: rows = logits[i]); top-K classes per row; CLIPScore
@@ -249,6 +258,17 @@ int rlcf_kd_loss(const float* student, int ld_s, const float* teacher, int ld_t,
 enum { RLCF_KD_SPLIT_MAX_ROWS = 65535 };
 int rlcf_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params,
                        float* loss, float* row_loss, float* dlogits, rlcf_stream stream);
+/* (ABI version 17) The loss of the TPT baseline (TPT/tpt_cls.py:40-46,66; TPT/tune_cls_tpt.py:49): avg_entropy of logits rows and its
+ * dense gradient, with no reward model.  `groups` independent samples of n consecutive rows each (rows [groups * n, C], row stride
+ * ld >= C): with p_ic = softmax(x_i)_c and a_c = log((1/n) sum_i p_ic), clamped below at float32's finfo.min as the reference clamps,
+ *   loss[g] = -sum_c a_c e^{a_c},   dlogits[i, d] = (p_id / n) * (sum_c p_ic a_c - a_d)        (dlogits dense [groups * n, C])
+ * Each output optional, one at least.  Evaluated in double and rounded to float once; fixed-order reductions, no atomics: two calls
+ * give the same bits and a group gives the same bits alone as inside a grouped call.  1 <= C <= RLCF_KD_MAX_CLASSES, n >= 1,
+ * groups <= 65535.  One class: loss 0, gradients 0.  A NaN / infinity in a row makes the loss and every gradient of its group
+ * non-finite.  ws: device scratch of rlcf_tpt_loss_ws_bytes(groups, n, C) bytes, or NULL = taken from the stream-ordered allocator
+ * of `stream`.  rlcf_reward_loss with RLCF_F_MIN_ENTROPY keeps its own float32 form of the same expression as a regulariser. */
+size_t rlcf_tpt_loss_ws_bytes(int groups, int n, int C);
+int rlcf_tpt_loss(const float* logits, int ld, int groups, int n, int C, float* loss, float* dlogits, void* ws, rlcf_stream stream);
 /* (ABI version 16) Recall ranks of LAVIS RetrievalTask._report_metrics: ranks[r] = the number of columns of score row r (scores
  * [rows, cols], row stride ld) that score STRICTLY higher than the best-scoring ground-truth column of that row.  gt_offsets != NULL:
  * CSR, row r owns gt_indices[gt_offsets[r] .. gt_offsets[r + 1]) (image -> text, several captions per image); gt_offsets == NULL:

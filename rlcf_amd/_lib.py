@@ -20,6 +20,7 @@ STUDENT, REWARD = 0, 1
 MAX_REWARDS = 4
 F_REWARD_PROCESS, F_AMPLIFY, F_PROCESS_BATCH, F_MIN_ENTROPY = 1, 2, 4, 8
 F_KD, F_DKD, F_ATKD, F_KD_MASK = 32, 64, 96, 96          # loss kind of the image-encoder tuning calls (0 = the RL reward loss)
+F_TPT = 128                                               # the TPT baseline: avg_entropy of the selected views in place of the reward loss
 KD_KD, KD_DKD, KD_ATKD = 1, 2, 3                          # rlcf_kd_loss modes (= the flag field >> 5)
 KD_MAX_CLASSES = 65536
 
@@ -96,6 +97,8 @@ SIGNATURES = {
     "rlcf_kd_loss": (I, [P, I, P, I, I, I, I, P, C.POINTER(KdParams), P, P, P, P]),
     "rlcf_kd_loss_split": (I, [P, I, P, I, I, I, C.POINTER(KdParams), P, P, P, P]),
     "rlcf_retrieval_ranks": (I, [P, I, I, I, P, P, P, P]),
+    "rlcf_tpt_loss": (I, [P, I, I, I, I, P, P, P, P]),
+    "rlcf_tpt_loss_ws_bytes": (C.c_size_t, [I, I, I]),
     "rlcf_adamw_step": (I, [P, P, P, P, I64, I, F, F, F, F, F, P]),
     "rlcf_engine_create": (P, [C.POINTER(ClipCfg), C.POINTER(ClipCfg), I, I, I]),
     "rlcf_engine_destroy": (None, [P]),

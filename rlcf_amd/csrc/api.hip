@@ -35,7 +35,7 @@ int rlcf_func_lds(const void* fn, size_t bytes) {
 extern "C" {
 
 const char* rlcf_last_error(void) { return g_err; }
-int rlcf_version(void) { return 16; }   // 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
+int rlcf_version(void) { return 17; }   // 17: the TPT baseline (rlcf_tpt_loss, RLCF_F_TPT on rlcf_tta_sample / _sample_ln / _sample_visual / _batch / _batch_ln: avg_entropy in place of the reward loss, an engine without a reward model); 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
 //    // 2: rlcf_clip_cfg.vision_stages, reward slots, views, LN batch; 3: rlcf_tta_out.vis_*, rlcf_tta_sample_visual
 
 // ------------------------------------------------------------------ op level
@@ -464,6 +464,20 @@ int rlcf_kd_loss_split(const float* student, int ld_s, const float* teacher, int
     (void)hipFreeAsync(ws, (hipStream_t)stream);
     return rc;
 }
+int rlcf_tpt_loss(const float* logits, int ld, int groups, int n, int C, float* loss, float* dlogits, void* ws, rlcf_stream stream) {
+    RLCF_ARG_CHECK(logits && (loss || dlogits));
+    if (groups <= 0 || n <= 0 || C <= 0 || C > RLCF_KD_MAX_CLASSES) {
+        rlcf_set_error("tpt_loss: %d groups of n = %d rows of C = %d classes (need groups >= 1, n >= 1, 1 <= C <= %d)", groups, n, C, RLCF_KD_MAX_CLASSES);
+        return RLCF_ERR_ARG;
+    }
+    if (ws) return launch_tpt_loss(logits, ld, groups, n, C, loss, dlogits, (double*)ws, (hipStream_t)stream);
+    double* own = nullptr;           // stateless call: the scratch comes from the stream-ordered allocator
+    RLCF_HIP_CHECK(hipMallocAsync((void**)&own, tpt_ws_bytes(groups, n, C), (hipStream_t)stream));
+    const int rc = launch_tpt_loss(logits, ld, groups, n, C, loss, dlogits, own, (hipStream_t)stream);
+    (void)hipFreeAsync(own, (hipStream_t)stream);
+    return rc;
+}
+size_t rlcf_tpt_loss_ws_bytes(int groups, int n, int C) { return groups > 0 && n > 0 && C > 0 ? tpt_ws_bytes(groups, n, C) : 0; }
 int rlcf_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_offsets, const int32_t* gt_indices, int32_t* ranks,
                          rlcf_stream stream) {
     return launch_retrieval_ranks(scores, ld, rows, cols, gt_offsets, gt_indices, ranks, (hipStream_t)stream);
@@ -477,6 +491,16 @@ static int kd_refused(const rlcf_tta_args* a, const char* entry) {
     }
     return RLCF_OK;
 }
+// the TPT loss exists on the one-image tuning calls and the two batched classification calls; the reference has no lane and no
+// retrieval form of it (TPT/tpt_cls.py, TPT/tune_cls_tpt.py)
+static int tpt_refused(const rlcf_tta_args* a, const char* entry) {
+    if (tpt_on(a)) {
+        rlcf_set_error("%s: the TPT loss (RLCF_F_TPT) runs on rlcf_tta_sample / rlcf_tta_sample_ln / rlcf_tta_sample_visual / rlcf_tta_batch / "
+                       "rlcf_tta_batch_ln only", entry);
+        return RLCF_ERR_ARG;
+    }
+    return RLCF_OK;
+}
 int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img, int n, const float* dlogits, float* dctx,
                              rlcf_stream stream) {
     RLCF_ARG_CHECK(e && ctx && img && dlogits && dctx && n > 0);
@@ -484,6 +508,7 @@ int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img,
 }
 int rlcf_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);
+    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_sample")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_sample")) return rc_;
     return engine_tta_sample(e, views, N, args, out, engine_stream(e, stream));
 }
@@ -497,6 +522,7 @@ int rlcf_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rlcf
 }
 int rlcf_tta_retrieval_image(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && images && args && n > 0);
+    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_image")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_image")) return rc_;
     rlcf_tta_args a = *args;
     a.selection_p = 1.0f; a.n_sel = n; a.flags |= RLCF_F_NO_SELECTION;     // every query image carries reward and gradient, in loader order
@@ -508,17 +534,20 @@ int rlcf_engine_set_image_bank(rlcf_engine* e, const float* student_feats, const
 }
 int rlcf_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && tokens_host && args);
+    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_text")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_text")) return rc_;
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_kd_params* kd,
                                 const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && images && args && n > 0);
+    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_image_kd")) return rc_;
     return engine_tta_retrieval_image_kd(e, images, n, args, kd, out, engine_stream(e, stream));
 }
 int rlcf_tta_retrieval_text_kd(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_kd_params* kd,
                                const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && tokens_host && args);
+    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_text_kd")) return rc_;
     const rlcf_kd_params p = kd ? *kd : kd_default_params();
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream), &p);
 }
@@ -745,12 +774,14 @@ int rlcf_engine_reset_visual_state(rlcf_engine* e, rlcf_stream stream) {
 int rlcf_tta_batch(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                    rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
+    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_batch")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_batch")) return rc_;
     return engine_tta_batch(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
 int rlcf_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                       rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
+    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_batch_ln")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_batch_ln")) return rc_;
     return engine_tta_batch_ln(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
@@ -819,6 +850,7 @@ rlcf_stream rlcf_lanes_stream(const rlcf_lanes* l, int k) { return (l && k >= 0 
 int rlcf_lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                       int norm_layers, rlcf_stream producer) {
     RLCF_ARG_CHECK(l && views && args && count > 0 && top5);
+    if (const int rc_ = tpt_refused(args, "rlcf_lanes_submit")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_lanes_submit")) return rc_;
     const int k = l->next;
     RLCF_HIP_CHECK(hipEventRecord(l->ready, (hipStream_t)producer));
@@ -838,6 +870,7 @@ int rlcf_lanes_join(rlcf_lanes* l, rlcf_stream consumer) {
 int rlcf_tta_lanes(rlcf_engine* const* engines, int lanes, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits,
                    int32_t* top5, int norm_layers, rlcf_stream stream) {
     RLCF_ARG_CHECK(engines && lanes >= 1 && views && args && count > 0 && top5);
+    if (const int rc_ = tpt_refused(args, "rlcf_tta_lanes")) return rc_;
     if (const int rc_ = kd_refused(args, "rlcf_tta_lanes")) return rc_;
     rlcf_lanes* l = rlcf_lanes_create(engines, lanes);
     if (!l) return RLCF_ERR_HIP;

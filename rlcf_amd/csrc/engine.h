@@ -242,6 +242,7 @@ struct rlcf_engine {
     DevBuf kd_teacher;               // [n_sel, C] the reward model's logits of the selected views (distillation losses, step 0 on)
     DevBuf kd_ws;                    // workspace of the split-row KD loss (kd_split_ws_bytes)
     int kd_teacher_rows = 0, kd_teacher_C = 0;   // what kd_teacher holds: rows x bank size of the last distillation call (0 after a new bank)
+    DevBuf tpt_ws;                   // workspace of the TPT loss (tpt_ws_bytes), RLCF_F_TPT
     DevBuf step_skip;                // int32 per test sample: gradient held an inf / NaN -> optimizer step skipped (GradScaler semantics)
     // packed class-sequence runs of the text pass being enqueued (set by text_forward around transformer_forward)
     const rlcf_seq* pk_cur = nullptr; int n_pk_cur = 0; const int32_t* rss_cur = nullptr;
@@ -322,6 +323,9 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
 int engine_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* a, const rlcf_kd_params* kd,
                                   const rlcf_tta_out* out, hipStream_t st);
 int engine_kd_refusals(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry);
+// RLCF_F_TPT (the TPT baseline: avg_entropy of the selected views in place of the reward loss, no reward model needed)
+static inline bool tpt_on(const rlcf_tta_args* a) { return a && (a->flags & RLCF_F_TPT) != 0; }
+int engine_tpt_check(const rlcf_tta_args* a, const char* entry);      // the flag combinations every entry that takes it refuses
 int engine_visual_refresh(rlcf_engine* e, hipStream_t st, bool at_checkpoint = false);   // at_checkpoint: the live weights ARE the checkpoint's (reset of a pristine initial state)
 int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                         hipStream_t st);

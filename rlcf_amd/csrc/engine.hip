@@ -1294,7 +1294,7 @@ static int tta_scratch_ensure(rlcf_engine* e, int C) {
     TRY(e->sel_logits.ensure((size_t)N * C * sizeof(float)));
     TRY(e->rl_stats.ensure(reward_loss_stats_floats(N) * sizeof(float)));          // scratch of the loss kernel: at most N selected rows
     TRY(e->step_skip.ensure((size_t)std::max(N, 64) * sizeof(int32_t)));             // non-finite-gradient flags, one per test sample of a pass
-    if (e->n_rewards > 0) {
+    {   // (also without a reward model: the image-encoder tuning calls re-run the selected views under RLCF_F_TPT)
         const int R = s.cfg.image_resolution;                // selected views are kept at the student's resolution
         TRY(e->views_sel.ensure((size_t)N * 3 * R * R * sizeof(float)));
     }

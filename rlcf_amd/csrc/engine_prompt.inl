@@ -90,23 +90,52 @@ static RewardBank reward_bank(const rlcf_engine* e) {
     return b;
 }
 
+// ------------------------------------------------------------------ the TPT baseline (TPT/tpt_cls.py:49-72, TPT/tune_cls_tpt.py:34-54)
+// RLCF_F_TPT exchanges the loss: avg_entropy of the selected views (tpt.hip) where the reward loss or a distillation loss stood;
+// selection, backward, step skip and AdamW are the RL path's.  No reward pass, no teacher, no top-K stage: an engine without a
+// reward model serves it.
+int engine_tpt_check(const rlcf_tta_args* a, const char* entry) {
+    if (!tpt_on(a)) return RLCF_OK;
+    if (a->flags & (RLCF_F_KD_MASK | RLCF_F_MIN_ENTROPY | RLCF_F_NO_SELECTION)) {
+        rlcf_set_error("%s: the TPT loss (RLCF_F_TPT) takes no distillation loss, no min-entropy regulariser and no retrieval rows (flags 0x%x)",
+                       entry, a->flags);
+        return RLCF_ERR_ARG;
+    }
+    return RLCF_OK;
+}
+// what every tuning entry asks of the engine's state and of sample_k (ignored under RLCF_F_TPT, which needs no reward model either)
+static int tta_state_check(const rlcf_engine* e, const rlcf_tta_args* a) {
+    if (e->C <= 0 || e->image_bank || (e->n_rewards <= 0 && !tpt_on(a))) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
+    return RLCF_OK;
+}
+static bool sample_k_ok(const rlcf_engine* e, const rlcf_tta_args* a) {
+    return tpt_on(a) || (a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+}
+// loss [groups] (optional) and dlogits of `groups` samples of n_sel rows of e->sel_logits, where the reward loss leaves them
+static int tpt_step(rlcf_engine* e, int groups, int n_sel, float* loss, hipStream_t st) {
+    TRY(e->tpt_ws.ensure(tpt_ws_bytes(groups, n_sel, e->C)));
+    return launch_tpt_loss(e->sel_logits.as<float>(), e->C, groups, n_sel, e->C, loss, e->dlogits.as<float>(), (double*)e->tpt_ws.p, st);
+}
+
 // Harness body TPT/tpt_cls_rl.py:251-262 around test_time_tuning (:47-79).
 #define COPY_OUT(dst, src, bytes) do { if (dst) RLCF_HIP_CHECK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st)); } while (0)
 int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    if (e->C <= 0 || e->image_bank || e->n_rewards <= 0) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
+    RLCF_ARG_CHECK(a);
+    TRY(tta_state_check(e, a));
     if (e->n_ctx <= 0) { rlcf_set_error("prompt tuning needs a class bank with learnable context rows (n_ctx > 0)"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a && a->tta_steps >= 0 && a->sample_k > 0 && a->sample_k <= 32);
-    const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, n_ctx = e->n_ctx;
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->tta_steps >= 0 && sample_k_ok(e, a));
+    TRY(engine_tpt_check(a, "rlcf_tta_sample"));
+    const bool tpt = tpt_on(a);
+    const int C = e->C, K = tpt ? 1 : a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, n_ctx = e->n_ctx;
     const int n_sel = n_selected(a, N);                       // int() truncation, tpt_cls_rl.py:34
-    RLCF_ARG_CHECK(K <= C);
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
     const size_t cb = (size_t)n_ctx * Wt * sizeof(float);
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const rlcf_tta_out none{};
     if (!out) out = &none;
     const bool sparse_ok = a->sparse_backward && (a->flags & RLCF_F_REWARD_PROCESS) && !(a->flags & RLCF_F_PROCESS_BATCH) &&
-                           !(a->flags & RLCF_F_MIN_ENTROPY) && K > 1;
+                           !(a->flags & RLCF_F_MIN_ENTROPY) && K > 1 && !tpt;      // (the TPT loss is dense over the classes)
     const int n_e = n_sel * K;
     if (a->tta_steps > 0) {
         if (sparse_ok) TRY(sparse_ensure(e, n_e, st));
@@ -165,7 +194,7 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
                     if (er != hipSuccess) { (void)hipStreamSynchronize(e->side); rlcf_set_error("hipEventRecord(ev_join): %s", hipGetErrorString(er)); return RLCF_ERR_HIP; }
                     return rc_side;
                 }
-            } else {
+            } else if (!tpt) {
                 TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
             }
             TRY(launch_gather_rows(e->logits.as<float>(), C, e->sel_idx.as<int32_t>(), e->sel_logits.as<float>(), C, n_sel, C, st));
@@ -187,7 +216,8 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
             TRY(engine_logits(e, e->sel_feat.as<float>(), n_sel, txt_j, C, e->sel_logits.as<float>(), st));
             rows_logits = e->sel_logits.as<float>();
         }
-        TRY(launch_reward_loss_bank(rows_logits, C, nullptr, 1, n_sel, C, K, reward_bank(e),
+        if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));         // (rows_logits is e->sel_logits at every step)
+        else TRY(launch_reward_loss_bank(rows_logits, C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
         if (sparse_ok && fwd_done) {
@@ -202,9 +232,11 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
                               e->lay[0].ctx_rows_list.as<int32_t>(), e->lay[0].n_copies, n_ctx, e->ctx_grad.as<float>(), st));
         }
         if (j == 0) {
-            COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-            COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-            COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            if (!tpt) {          // (the TPT loss samples no classes: topk_idx / clip_score / rewards stay unwritten)
+                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
+                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
+                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+            }
             COPY_OUT(out->loss, e->loss.p, sizeof(float));
             COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
             COPY_OUT(out->ctx_grad, e->ctx_grad.p, cb);
@@ -402,13 +434,14 @@ static int tta_batch_pipelined(rlcf_engine* e, const float* views, int B, int N,
 int engine_tta_batch(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                      hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    if (e->C <= 0 || e->image_bank || e->n_rewards <= 0) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
+    TRY(tta_state_check(e, a));
     if (e->n_ctx <= 0) { rlcf_set_error("prompt tuning needs a class bank with learnable context rows (n_ctx > 0)"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && sample_k_ok(e, a));
+    TRY(engine_tpt_check(a, "rlcf_tta_batch"));
     const size_t per = (size_t)N * 3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const int n_sel = n_selected(a, N);
     const bool sparse_ok = a->sparse_backward && (a->flags & RLCF_F_REWARD_PROCESS) && !(a->flags & RLCF_F_PROCESS_BATCH) &&
-                           !(a->flags & RLCF_F_MIN_ENTROPY) && a->sample_k > 1;
+                           !(a->flags & RLCF_F_MIN_ENTROPY) && a->sample_k > 1 && !tpt_on(a);      // (RLCF_F_TPT: dense backward, sample by sample)
     const int Bmax = e->max_views / N;
     const bool fused = Bmax >= 2 && a->tta_steps >= 1 && sparse_ok && !a->ctx_in && !a->skip_final && n_sel > 0;
     double flops = 0.0;

@@ -78,6 +78,7 @@ static int vit_backward_ln(rlcf_engine* e, ClipModel& m, const float* feats, int
 static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                               hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
+    const bool tpt = tpt_on(a);
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), BN = B * N, BS = B * n_sel;
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
@@ -93,7 +94,7 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
     TRY(engine_logits(e, e->img_feat.as<float>(), BN, cls_feat, C, e->logits.as<float>(), st));
     TRY(launch_entropy_select_batched(e->logits.as<float>(), B, N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
     TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, BS, (int)img_elems, st));
-    TRY(reward_encode(e, BS, s.cfg.image_resolution, nullptr, st));
+    if (!tpt) TRY(reward_encode(e, BS, s.cfg.image_resolution, nullptr, st));
     // reset state of every sample (custom_clip.py:456-458 + optimizer.load_state_dict)
     TRY(launch_broadcast_rows(e->ln_init.as<float>(), e->b_ln.as<float>(), (int)np, B, st));
     RLCF_HIP_CHECK(hipMemsetAsync(e->b_ln_m.p, 0, B * nb, st));
@@ -104,7 +105,8 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
         e->lng_base = e->b_ln.as<float>(); e->lng_views = n_sel;
         int rc = vit_forward_saved(e, s, e->views_sel.as<float>(), BS, e->ln_feat.as<float>(), st);
         if (rc == RLCF_OK) rc = engine_logits(e, e->ln_feat.as<float>(), BS, cls_feat, C, e->sel_logits.as<float>(), st);
-        if (rc == RLCF_OK) rc = launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, B, n_sel, C, K, reward_bank(e), a->clipscore_weight,
+        if (rc == RLCF_OK && tpt) rc = tpt_step(e, B, n_sel, nullptr, st);          // one group per sample
+        else if (rc == RLCF_OK) rc = launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, B, n_sel, C, K, reward_bank(e), a->clipscore_weight,
                                                         a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), nullptr, nullptr, nullptr,
                                                         e->dlogits.as<float>(), e->rl_stats.as<float>(), st);
         if (rc == RLCF_OK) rc = vit_backward_ln(e, s, e->ln_feat.as<float>(), BS, e->dlogits.as<float>(), e->b_ln_grad.as<float>(), st, B);
@@ -131,8 +133,9 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
 int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                         hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    if (e->C <= 0 || e->image_bank || e->n_rewards <= 0) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+    TRY(tta_state_check(e, a));
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && sample_k_ok(e, a));
+    TRY(engine_tpt_check(a, "rlcf_tta_batch_ln"));
     const bool rn = is_resnet(s.cfg);         // BatchNorm tuning: the batch statistics couple one sample's views, samples run one by one
     RLCF_ARG_CHECK(rn || s.tokens <= 320);
     const size_t per = (size_t)N * 3 * s.cfg.image_resolution * s.cfg.image_resolution;
@@ -253,7 +256,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
     const size_t vb = full ? e->vw_count * sizeof(float) : 0;
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
-    const bool kd = kd_mode(a) != 0;
+    const bool kd = kd_mode(a) != 0, tpt = tpt_on(a);
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const size_t nb = (size_t)e->ln_count * sizeof(float);
     const rlcf_tta_out none{};
@@ -281,7 +284,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
             TRY(engine_logits(e, e->ln_feat.as<float>(), N, cls_feat, C, e->logits.as<float>(), st));
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
-            TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (!tpt) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
             if (kd) TRY(kd_teacher(e, n_sel, st));
             TRY(launch_gather_rows(e->logits.as<float>(), C, e->sel_idx.as<int32_t>(), e->sel_logits.as<float>(), C, n_sel, C, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
@@ -291,6 +294,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
             TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
         }
         if (kd) TRY(kd_step(e, n_sel, a, st));
+        else if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));
         else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
@@ -305,7 +309,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         TRY(rn_backward_bn(e, s, n, e->ln_feat.as<float>(), e->dfeat.as<float>(), e->ln_grad.as<float>(), st, full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            if (!kd) {           // (the distillation losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
+            if (!kd && !tpt) {   // (the distillation and TPT losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
                 COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
                 COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
                 COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
@@ -361,8 +365,11 @@ static int visual_reset(rlcf_engine* e, hipStream_t st) {      // visual.load_st
 static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full,
                                const rlcf_kd_params* rkd) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    if (e->C <= 0 || e->image_bank || e->n_rewards <= 0) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a && a->tta_steps >= 0 && a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+    RLCF_ARG_CHECK(a);
+    TRY(tta_state_check(e, a));
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->tta_steps >= 0 && sample_k_ok(e, a));
+    TRY(engine_tpt_check(a, full ? "rlcf_tta_sample_visual" : "rlcf_tta_sample_ln"));
+    const bool tpt = tpt_on(a);
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
@@ -398,7 +405,7 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             if (a->flags & RLCF_F_NO_SELECTION) TRY(launch_iota(e->sel_idx.as<int32_t>(), n_sel, st));     // retrieval: every row, in order
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
-            TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (!tpt) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
             if (kd) TRY(kd_teacher(e, n_sel, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
             COPY_OUT(out->entropy, e->entropy.p, N * sizeof(float));
@@ -407,6 +414,7 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
         TRY(vit_forward_saved(e, s, e->views_sel.as<float>(), n_sel, e->ln_feat.as<float>(), st));
         TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
         if (kd) TRY(kd_step(e, n_sel, a, st, rkd));
+        else if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));
         else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
                                a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
                                e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
@@ -415,7 +423,7 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
                             full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            if (!kd) {           // (the distillation losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
+            if (!kd && !tpt) {   // (the distillation and TPT losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
                 COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
                 COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
                 COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));

@@ -146,6 +146,10 @@ int launch_kd_loss(const float* student, int ld_s, const float* teacher, int ld_
 size_t kd_split_ws_bytes(int n, int C);
 int launch_kd_loss_split(const float* student, int ld_s, const float* teacher, int ld_t, int n, int C, const rlcf_kd_params* params, float* loss,
                          float* row_loss, float* dlogits, float* dot, double* ws, hipStream_t st);
+// avg_entropy of `groups` samples of n consecutive rows and its dense gradient (tpt.hip): loss [groups] and dlogits [groups * n, C], each
+// optional (one at least); ws = caller-owned scratch of tpt_ws_bytes(groups, n, C) bytes
+size_t tpt_ws_bytes(int groups, int n, int C);
+int launch_tpt_loss(const float* logits, int ld, int groups, int n, int C, float* loss, float* dlogits, double* ws, hipStream_t st);
 // recall ranks of score rows (kd.hip): gt_off = CSR offsets [rows + 1] or NULL (one ground-truth index per row)
 int launch_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_off, const int32_t* gt_idx, int32_t* ranks,
                            hipStream_t st);

@@ -64,11 +64,12 @@ class TTAConfig:
     min_entropy_w: float = 0.1           # TPT/params.py:66
     sparse_backward: bool = True
     kd_loss: Optional[str] = None        # --kd_loss of TPT/tune_cls_kd.py: "KD" / "DKD" / "ATKD" replace the reward loss (None = RL)
+    tpt: bool = False                    # the TPT baseline (TPT/tpt_cls.py, tune_cls_tpt.py): avg_entropy replaces the reward loss, no reward model
 
     def flags(self) -> int:
         return ((L.F_REWARD_PROCESS if self.reward_process else 0) | (L.F_AMPLIFY if self.reward_amplify else 0) |
                 (L.F_PROCESS_BATCH if self.process_batch else 0) | (L.F_MIN_ENTROPY if self.min_entropy_reg else 0) |
-                kd_flag(self.kd_loss))
+                kd_flag(self.kd_loss) | (L.F_TPT if self.tpt else 0))
 
     def n_sel(self, n_views: int) -> int:
         """int(N * top) of select_confident_samples (TPT/tpt_cls_rl.py:34): Python's double product, truncated."""
@@ -99,6 +100,20 @@ def kd_loss_op(student: torch.Tensor, teacher: torch.Tensor, mode: int, target: 
     L.check(lib.rlcf_kd_loss(student.data_ptr(), student.stride(0), teacher.data_ptr(), teacher.stride(0), n, Cn, int(mode), _ptr(tg),
                              C.byref(params) if params is not None else None, _ptr(loss), _ptr(rows), _ptr(dlogits), _stream()), "kd_loss")
     return loss, dlogits, rows
+
+
+def tpt_loss_op(logits: torch.Tensor, groups: int = 1, want_loss: bool = True, want_dlogits: bool = True):
+    """One rlcf_tpt_loss call on float32 device rows [groups * n, C] (any row stride): avg_entropy per group of n consecutive rows and
+    its gradient -> (loss [groups] or None, dlogits [groups * n, C] or None)."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1, "float32 rows, contiguous within a row"
+    rows, Cn = logits.shape
+    assert groups >= 1 and rows % groups == 0
+    dev = logits.device
+    loss = torch.empty(groups, device=dev) if want_loss else None
+    dlogits = torch.empty(rows, Cn, device=dev) if want_dlogits else None
+    L.check(L.lib().rlcf_tpt_loss(logits.data_ptr(), logits.stride(0), groups, rows // groups, Cn, _ptr(loss), _ptr(dlogits), None, _stream()),
+            "tpt_loss")
+    return loss, dlogits
 
 
 def kd_loss_split_op(student: torch.Tensor, teacher: torch.Tensor, params: Optional[L.KdParams] = None, row_loss: bool = False):
@@ -261,6 +276,7 @@ class Engine:
                      loss=torch.empty(1, device=dev), dlogits=torch.empty(n_sel, Cn, device=dev),
                      ctx_grad=torch.empty(self.n_ctx, Wt, device=dev),
                      reward_image_features=torch.empty(n_sel * Dr, device=dev))
+            self._kd_outputs(o, cfg, n_sel)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         if ctx_in is not None:
             ctx_in = ctx_in.detach().to(dev, torch.float32).contiguous()
@@ -304,12 +320,15 @@ class Engine:
     def _kd_outputs(self, o: Dict[str, torch.Tensor], cfg: TTAConfig, n_sel: int) -> None:
         """a distillation-loss call samples no classes (topk_idx / clip_score / rewards stay unwritten, so they are not returned);
         it returns the first step's dlogits and the reward features of the selected views, the teacher's input"""
-        if not cfg.kd_loss:
+        if not cfg.kd_loss and not cfg.tpt:
             return
         for k in ("topk_idx", "clip_score", "rewards"):
             o.pop(k, None)
         o["dlogits"] = torch.empty(n_sel, self.n_cls, device=self.device)
-        o["reward_image_features"] = torch.empty(n_sel, self.reward.embed_dim, device=self.device)
+        if cfg.tpt:                    # (no reward pass under RLCF_F_TPT: reward_image_features stays unwritten too)
+            o.pop("reward_image_features", None)
+        else:
+            o["reward_image_features"] = torch.empty(n_sel, self.reward.embed_dim, device=self.device)
 
     def kd_loss(self, student: torch.Tensor, teacher: torch.Tensor, kind: str = "KD", target: Optional[torch.Tensor] = None,
                 params: Optional[L.KdParams] = None, row_loss: bool = False):

@@ -44,9 +44,12 @@ def avg_entropy(outputs):
     return -(avg_logits * torch.exp(avg_logits)).sum(dim=-1)
 
 
-def _config(args, optimizer, reward_model) -> TTAConfig:
+def _config(args, optimizer, reward_model, tpt=False) -> TTAConfig:
     g = optimizer.param_groups[0]
     b1, b2 = g.get("betas", (0.9, 0.999))
+    if tpt:            # the TPT baseline reads no reward-model setting (tune_cls_tpt.py passes reward_model=None)
+        return TTAConfig(selection_p=args.selection_p, tta_steps=args.tta_steps, lr=g["lr"], weight_decay=g.get("weight_decay", 0.0),
+                         beta1=b1, beta2=b2, eps=g.get("eps", 1e-8), tpt=True)
     return TTAConfig(selection_p=args.selection_p, tta_steps=args.tta_steps, sample_k=reward_model.sample_k, lr=g["lr"],
                      weight_decay=g.get("weight_decay", 0.0), beta1=b1, beta2=b2, eps=g.get("eps", 1e-8),
                      reward_process=bool(reward_model.reward_process), process_batch=bool(reward_model.process_batch),
@@ -55,21 +58,25 @@ def _config(args, optimizer, reward_model) -> TTAConfig:
                      min_entropy_w=float(getattr(args, "min_entropy_w", 0.1)))
 
 
-def test_time_tuning(model, inputs, optimizer, scaler, args, reward_model=None, kd_loss=None):
+def test_time_tuning(model, inputs, optimizer, scaler, args, reward_model=None, kd_loss=None, tpt=False):
     """TPT/tpt_cls_rl.py:47-79.  `optimizer` supplies the AdamW hyper-parameters (its state is reset per
     sample by the harness, :255, so the fused step starts from step 1); `scaler` is accepted and unused:
     the HIP path computes in f32-grade precision, there is no loss scaling to apply.
     kd_loss ("KD" / "DKD" / "ATKD", not in the reference's signature): the distillation loss of TPT/tune_cls_kd.py:34-61 in place of
-    the reward loss (rlcf_amd.tune_cls_kd passes it; the `--kd_loss` flag itself is read by that entry point only)."""
+    the reward loss (rlcf_amd.tune_cls_kd passes it; the `--kd_loss` flag itself is read by that entry point only).
+    tpt (not in the reference's signature either): the TPT baseline, avg_entropy of the selected views in place of the reward loss
+    (rlcf_amd.tpt_cls / rlcf_amd.tune_cls_tpt pass it); the one form in which reward_model may be None."""
     # the tensor test_time_adapt_eval will pass to model(image) next (row 0 of `inputs`): consumed HERE, whatever happens below — an early
     # return or an exception must not leave it behind for an unrelated later call
     hint = getattr(model, "_clean_view_hint", None)
     model._clean_view_hint = None
-    if reward_model is None:
+    if reward_model is None and not tpt:
         raise ValueError("RLCF needs a reward model (get_reward_model)")
+    if tpt and kd_loss is not None:
+        raise ValueError("tpt and kd_loss exclude each other")
     if args.tta_steps <= 0:
         return
-    cfg = _config(args, optimizer, reward_model)
+    cfg = _config(args, optimizer, reward_model, tpt)
     if kd_loss is not None:
         if hasattr(model, "prompt_learner"):
             raise NotImplementedError("the distillation losses tune the image encoder (CLIPCLS_TTA); tune_cls_kd.py has no prompt form")
@@ -155,10 +162,10 @@ def _hits(top5: torch.Tensor, targets, hits: torch.Tensor) -> None:
     L.check(L.lib().rlcf_top5_hits(top5.data_ptr(), t.data_ptr(), top5.shape[0], hits.data_ptr(), torch.cuda.current_stream().cuda_stream), "top5_hits")
 
 
-def _eval_batched(val_loader, model, optimizer, args, reward_model, images_per_pass):
+def _eval_batched(val_loader, model, optimizer, args, reward_model, images_per_pass, tpt=False):
     """Throughput form of the harness: test images are independent units (per-sample reset, tpt_cls_rl.py:251-255), so
     `images_per_pass` of them share every tower pass inside the engine (rlcf_tta_batch / rlcf_tta_batch_ln); same predictions."""
-    cfg = _config(args, optimizer, reward_model)
+    cfg = _config(args, optimizer, reward_model, tpt)
     prompt = hasattr(model, "prompt_learner")
     n, hits, buf, tgt = 0, None, [], []
 
@@ -286,24 +293,29 @@ def _loop_option(value, args, name):
 
 
 def test_time_adapt_eval(val_loader, model, optimizer, optim_state, scaler, args, device=None, reward_model=None, images_per_pass=None, in_flight=None,
-                         kd_loss=None):
+                         kd_loss=None, tpt=False):
     """TPT/tpt_cls_rl.py:219-279 and its twin TPT/tune_cls_rl.py:183-256 (CLIPCLS_TTA models: model.train() / model.eval() round the
     tuning step, :216-218, and model.momentum_update_model() after the clean-view inference, :240): per test image
     reset -> tune -> clean-view inference -> (EMA) -> top-1/top-5.
     `images_per_pass > 1` (not in the reference) hands that many test images to the engine at once; `in_flight > 1` (not in the reference
     either) keeps one image per engine call and runs that many samples side by side on their own engines and streams (_eval_in_flight).
     Both need independent samples: no cross-sample EMA, no per-sample encoder weights.
-    kd_loss: the loop of TPT/tune_cls_kd.py:191-236 (the same body, the tuning step distilling instead; one image per call)."""
+    kd_loss: the loop of TPT/tune_cls_kd.py:191-236 (the same body, the tuning step distilling instead; one image per call).
+    tpt: the loops of TPT/tpt_cls.py:242-314 and TPT/tune_cls_tpt.py:184-240 (the same body, avg_entropy as the loss, reward_model may be
+    None).  images_per_pass > 1 serves the prompt learner (the engine loops over the samples) and norm-layer tuning of a ViT student
+    (one fused pass); in_flight > 1 is not built for it."""
     images_per_pass, in_flight = _loop_option(images_per_pass, args, "images_per_pass"), _loop_option(in_flight, args, "in_flight")
     if kd_loss is not None and (images_per_pass > 1 or in_flight > 1):
         raise NotImplementedError("the distillation losses run one test image per engine call (images_per_pass = in_flight = 1)")
+    if tpt and in_flight > 1:
+        raise NotImplementedError("the TPT baseline has no in-flight form (in_flight = 1): rlcf_lanes_submit refuses RLCF_F_TPT")
     backbone = not hasattr(model, "prompt_learner")                 # CLIPCLS_TTA: the tune_cls_rl.py form of the loop
     full_visual = not hasattr(model, "prompt_learner") and not model.only_norm      # per-sample weights: one sample per pass
     if images_per_pass > 1 and args.tta_steps > 0 and not getattr(model, "momentum_update", False) and not full_visual:
         model.eval()
         with torch.no_grad():
             model.reset()
-        return _eval_batched(val_loader, model, optimizer, args, reward_model, images_per_pass)
+        return _eval_batched(val_loader, model, optimizer, args, reward_model, images_per_pass, tpt)
     if in_flight > 1 and args.tta_steps > 0 and not getattr(model, "momentum_update", False) and not full_visual and not (
             backbone and runtime.SESSION.reset_state_moved()):      # (an earlier EMA run left lane 0 another reset state than the lanes built from the checkpoint: serial loop)
         model.eval()
@@ -341,7 +353,7 @@ def test_time_adapt_eval(val_loader, model, optimizer, optim_state, scaler, args
             model.train()                                           # tune_cls_rl.py:216
         elif args.tpt and image is not images and image.dim() == 4 and image.size(0) == 1:
             model._clean_view_hint = image                          # images = cat([image, views...]): row 0 of the step's input IS this tensor
-        test_time_tuning(model, images, optimizer, scaler, args, reward_model=reward_model, kd_loss=kd_loss)
+        test_time_tuning(model, images, optimizer, scaler, args, reward_model=reward_model, kd_loss=kd_loss, tpt=tpt)
         if backbone:
             model.eval()                                            # tune_cls_rl.py:218
         with torch.no_grad():
