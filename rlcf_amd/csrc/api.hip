@@ -482,25 +482,11 @@ int rlcf_retrieval_ranks(const float* scores, int ld, int rows, int cols, const 
                          rlcf_stream stream) {
     return launch_retrieval_ranks(scores, ld, rows, cols, gt_offsets, gt_indices, ranks, (hipStream_t)stream);
 }
-// the distillation loss kinds exist only on the one-image image-encoder tuning calls (tune_cls_kd.py has no prompt, batched, lane
-// or retrieval form)
-static int kd_refused(const rlcf_tta_args* a, const char* entry) {
-    if (a && (a->flags & RLCF_F_KD_MASK)) {
-        rlcf_set_error("%s: the distillation losses (RLCF_F_KD / DKD / ATKD) run on rlcf_tta_sample_ln / rlcf_tta_sample_visual only", entry);
-        return RLCF_ERR_ARG;
-    }
-    return RLCF_OK;
-}
-// the TPT loss exists on the one-image tuning calls and the two batched classification calls; the reference has no lane and no
-// retrieval form of it (TPT/tpt_cls.py, TPT/tune_cls_tpt.py)
-static int tpt_refused(const rlcf_tta_args* a, const char* entry) {
-    if (tpt_on(a)) {
-        rlcf_set_error("%s: the TPT loss (RLCF_F_TPT) runs on rlcf_tta_sample / rlcf_tta_sample_ln / rlcf_tta_sample_visual / rlcf_tta_batch / "
-                       "rlcf_tta_batch_ln only", entry);
-        return RLCF_ERR_ARG;
-    }
-    return RLCF_OK;
-}
+// The tuning entries: each states which losses it has a form of and what it is (tta_args_check holds the rules), once, here.
+#define KINDS_RL LOSS_BIT(LOSS_RL)
+#define KINDS_RL_TPT (LOSS_BIT(LOSS_RL) | LOSS_BIT(LOSS_TPT))
+#define KINDS_ALL (KINDS_RL_TPT | LOSS_BIT(LOSS_KD) | LOSS_BIT(LOSS_DKD) | LOSS_BIT(LOSS_ATKD))
+#define TTA_CHECK(e, args, entry, kinds, what) do { const int rc_ = tta_args_check((e), (args), (entry), (kinds), (what)); if (rc_ != RLCF_OK) return rc_; } while (0)
 int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img, int n, const float* dlogits, float* dctx,
                              rlcf_stream stream) {
     RLCF_ARG_CHECK(e && ctx && img && dlogits && dctx && n > 0);
@@ -508,22 +494,22 @@ int rlcf_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img,
 }
 int rlcf_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);
-    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_sample")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_sample")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_sample", KINDS_RL_TPT, TTA_PROMPT);
     return engine_tta_sample(e, views, N, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);
+    TTA_CHECK(e, args, "rlcf_tta_sample_ln", KINDS_ALL, 0);
     return engine_tta_sample_ln(e, views, N, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);
+    TTA_CHECK(e, args, "rlcf_tta_sample_visual", KINDS_ALL, 0);
     return engine_tta_sample_visual(e, views, N, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_retrieval_image(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && images && args && n > 0);
-    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_image")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_image")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_retrieval_image", KINDS_RL, TTA_ROWS_IN_ORDER);
     rlcf_tta_args a = *args;
     a.selection_p = 1.0f; a.n_sel = n; a.flags |= RLCF_F_NO_SELECTION;     // every query image carries reward and gradient, in loader order
     return engine_tta_sample_visual(e, images, n, &a, out, engine_stream(e, stream));
@@ -534,20 +520,19 @@ int rlcf_engine_set_image_bank(rlcf_engine* e, const float* student_feats, const
 }
 int rlcf_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && tokens_host && args);
-    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_text")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_retrieval_text")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_retrieval_text", KINDS_RL, TTA_IMAGE_BANK);
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream));
 }
 int rlcf_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* args, const rlcf_kd_params* kd,
                                 const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && images && args && n > 0);
-    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_image_kd")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_retrieval_image_kd", LOSS_BIT(LOSS_KD), TTA_DISTILS | TTA_ROWS_IN_ORDER);
     return engine_tta_retrieval_image_kd(e, images, n, args, kd, out, engine_stream(e, stream));
 }
 int rlcf_tta_retrieval_text_kd(rlcf_engine* e, const int32_t* tokens_host, const rlcf_tta_args* args, const rlcf_kd_params* kd,
                                const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && tokens_host && args);
-    if (const int rc_ = tpt_refused(args, "rlcf_tta_retrieval_text_kd")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_retrieval_text_kd", LOSS_BIT(LOSS_KD), TTA_DISTILS | TTA_ROWS_IN_ORDER | TTA_IMAGE_BANK);
     const rlcf_kd_params p = kd ? *kd : kd_default_params();
     return engine_tta_retrieval_text(e, tokens_host, args, out, engine_stream(e, stream), &p);
 }
@@ -774,15 +759,13 @@ int rlcf_engine_reset_visual_state(rlcf_engine* e, rlcf_stream stream) {
 int rlcf_tta_batch(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                    rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
-    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_batch")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_batch")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_batch", KINDS_RL_TPT, TTA_PROMPT);
     return engine_tta_batch(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
 int rlcf_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
                       rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args && count > 0 && top5);
-    if (const int rc_ = engine_tpt_check(args, "rlcf_tta_batch_ln")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_batch_ln")) return rc_;
+    TTA_CHECK(e, args, "rlcf_tta_batch_ln", KINDS_RL_TPT, 0);
     return engine_tta_batch_ln(e, views, count, N, args, final_logits, top5, engine_stream(e, stream));
 }
 // ------------------------------------------------------------------ samples in flight (ABI 14)
@@ -847,12 +830,12 @@ static rlcf_lanes* lanes_create(rlcf_engine* const* engines, int n, const rlcf_s
 }
 int rlcf_lanes_count(const rlcf_lanes* l) { return l ? (int)l->eng.size() : 0; }
 rlcf_stream rlcf_lanes_stream(const rlcf_lanes* l, int k) { return (l && k >= 0 && k < (int)l->st.size()) ? (rlcf_stream)l->st[k] : nullptr; }
-int rlcf_lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
-                      int norm_layers, rlcf_stream producer) {
+// entry: the public call this submit belongs to (the name its refusals carry)
+static int lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
+                        int norm_layers, rlcf_stream producer, const char* entry) {
     RLCF_ARG_CHECK(l && views && args && count > 0 && top5);
-    if (const int rc_ = tpt_refused(args, "rlcf_lanes_submit")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_lanes_submit")) return rc_;
     const int k = l->next;
+    TTA_CHECK(l->eng[k], args, entry, KINDS_RL, norm_layers ? 0 : TTA_PROMPT);
     RLCF_HIP_CHECK(hipEventRecord(l->ready, (hipStream_t)producer));
     RLCF_HIP_CHECK(hipStreamWaitEvent(l->st[k], l->ready, 0));
     rlcf_engine* e = l->eng[k];
@@ -862,6 +845,10 @@ int rlcf_lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const
     l->next = (k + 1) % (int)l->eng.size();
     return rc < 0 ? rc : k;
 }
+int rlcf_lanes_submit(rlcf_lanes* l, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits, int32_t* top5,
+                      int norm_layers, rlcf_stream producer) {
+    return lanes_submit(l, views, count, N, args, final_logits, top5, norm_layers, producer, "rlcf_lanes_submit");
+}
 int rlcf_lanes_join(rlcf_lanes* l, rlcf_stream consumer) {
     RLCF_ARG_CHECK(l);
     for (size_t k = 0; k < l->st.size(); ++k) RLCF_HIP_CHECK(hipStreamWaitEvent((hipStream_t)consumer, l->done[k], 0));
@@ -870,16 +857,14 @@ int rlcf_lanes_join(rlcf_lanes* l, rlcf_stream consumer) {
 int rlcf_tta_lanes(rlcf_engine* const* engines, int lanes, const float* views, int count, int N, const rlcf_tta_args* args, float* final_logits,
                    int32_t* top5, int norm_layers, rlcf_stream stream) {
     RLCF_ARG_CHECK(engines && lanes >= 1 && views && args && count > 0 && top5);
-    if (const int rc_ = tpt_refused(args, "rlcf_tta_lanes")) return rc_;
-    if (const int rc_ = kd_refused(args, "rlcf_tta_lanes")) return rc_;
     rlcf_lanes* l = rlcf_lanes_create(engines, lanes);
     if (!l) return RLCF_ERR_HIP;
     const rlcf_clip_cfg& c = engines[0]->model[RLCF_STUDENT].cfg;
     const size_t per = (size_t)N * 3 * c.image_resolution * c.image_resolution;
     int rc = RLCF_OK;
     for (int i = 0; i < count && rc >= 0; ++i)
-        rc = rlcf_lanes_submit(l, views + (size_t)i * per, 1, N, args, final_logits ? final_logits + (size_t)i * engines[0]->C : nullptr, top5 + (size_t)i * 5,
-                               norm_layers, stream);
+        rc = lanes_submit(l, views + (size_t)i * per, 1, N, args, final_logits ? final_logits + (size_t)i * engines[0]->C : nullptr, top5 + (size_t)i * 5,
+                          norm_layers, stream, "rlcf_tta_lanes");
     const int rj = rlcf_lanes_join(l, stream);
     rlcf_lanes_destroy(l);               // (waits for the lanes: this convenience form is synchronous at its end; a loop keeps a lanes object)
     return rc < 0 ? rc : rj;

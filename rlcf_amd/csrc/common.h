@@ -47,6 +47,36 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+// sum / max over a workgroup of THREADS threads, the same value in every thread: the wave's xor-shuffle tree, lane 0 of each wave
+// to red[THREADS / 64] (LDS), a serial combine over the waves in index order — a fixed order, so two launches give the same bits
+template <int THREADS, typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = 0;
+    for (int i = 0; i < THREADS / 64; ++i) s += red[i];
+    return s;
+}
+template <int THREADS, typename T> __device__ __forceinline__ T block_max(T v, T* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = red[0];
+    for (int i = 1; i < THREADS / 64; ++i) s = fmax(s, red[i]);      // (the float overload is fmaxf)
+    return s;
+}
 // row of a 32x32 MFMA accumulator register r held by a lane in half h (cdna guide §3)
 __device__ __forceinline__ int mfma32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 

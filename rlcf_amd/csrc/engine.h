@@ -238,11 +238,10 @@ struct rlcf_engine {
     // the caller's streams this engine has enqueued work on (api.hip: engine_stream; a handful at most — a lane uses one): what
     // rlcf_engine_destroy waits for, instead of the whole device
     std::vector<hipStream_t> used_streams;
-    DevBuf rl_stats;                 // per-row scratch of the reward / loss kernels
+    DevBuf rl_stats;                 // per-row float scratch of the reward loss kernels (reward_loss_stats_floats, sized at set_class_bank)
+    DevBuf loss_ws;                  // double scratch of the distillation / TPT loss kernels (one per row, kd_split_ws_bytes, tpt_ws_bytes)
     DevBuf kd_teacher;               // [n_sel, C] the reward model's logits of the selected views (distillation losses, step 0 on)
-    DevBuf kd_ws;                    // workspace of the split-row KD loss (kd_split_ws_bytes)
     int kd_teacher_rows = 0, kd_teacher_C = 0;   // what kd_teacher holds: rows x bank size of the last distillation call (0 after a new bank)
-    DevBuf tpt_ws;                   // workspace of the TPT loss (tpt_ws_bytes), RLCF_F_TPT
     DevBuf step_skip;                // int32 per test sample: gradient held an inf / NaN -> optimizer step skipped (GradScaler semantics)
     // packed class-sequence runs of the text pass being enqueued (set by text_forward around transformer_forward)
     const rlcf_seq* pk_cur = nullptr; int n_pk_cur = 0; const int32_t* rss_cur = nullptr;
@@ -322,10 +321,21 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
                               const rlcf_kd_params* kd = nullptr);       // kd != NULL: the distillation form (clip_ret_kd.py:70-92)
 int engine_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* a, const rlcf_kd_params* kd,
                                   const rlcf_tta_out* out, hipStream_t st);
-int engine_kd_refusals(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry);
-// RLCF_F_TPT (the TPT baseline: avg_entropy of the selected views in place of the reward loss, no reward model needed)
-static inline bool tpt_on(const rlcf_tta_args* a) { return a && (a->flags & RLCF_F_TPT) != 0; }
-int engine_tpt_check(const rlcf_tta_args* a, const char* entry);      // the flag combinations every entry that takes it refuses
+// the loss a tuning call runs, from its flags: the reward loss, a distillation loss against the reward model's logits (the value is
+// rlcf_kd_loss's mode), or the TPT baseline (avg_entropy of the selected views, no reward model needed)
+enum LossKind { LOSS_RL = 0, LOSS_KD = RLCF_KD_KD, LOSS_DKD = RLCF_KD_DKD, LOSS_ATKD = RLCF_KD_ATKD, LOSS_TPT };
+static inline LossKind loss_kind(const rlcf_tta_args* a) {
+    return (a->flags & RLCF_F_TPT) ? LOSS_TPT : (LossKind)((a->flags & RLCF_F_KD_MASK) >> 5);
+}
+static inline bool loss_distils(LossKind k) { return k == LOSS_KD || k == LOSS_DKD || k == LOSS_ATKD; }
+// what a tuning entry is, for tta_args_check
+enum { TTA_PROMPT = 1,           // tunes the prompt: the class bank needs learnable context rows
+       TTA_ROWS_IN_ORDER = 2,    // retrieval: every row in order (RLCF_F_NO_SELECTION is the entry's own)
+       TTA_IMAGE_BANK = 4,       // the bank holds image features (rlcf_engine_set_image_bank), not class / caption texts
+       TTA_DISTILS = 8 };        // a retrieval distillation entry: the loss is KD whatever the flags' kind field says
+#define LOSS_BIT(k) (1u << (k))
+// every rule on (entry, loss kind, flags, engine state) of the tuning entries, checked once per call before anything is launched
+int tta_args_check(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry, unsigned kinds, unsigned what);
 int engine_visual_refresh(rlcf_engine* e, hipStream_t st, bool at_checkpoint = false);   // at_checkpoint: the live weights ARE the checkpoint's (reset of a pristine initial state)
 int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                         hipStream_t st);

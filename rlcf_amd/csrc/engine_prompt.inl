@@ -90,44 +90,133 @@ static RewardBank reward_bank(const rlcf_engine* e) {
     return b;
 }
 
-// ------------------------------------------------------------------ the TPT baseline (TPT/tpt_cls.py:49-72, TPT/tune_cls_tpt.py:34-54)
-// RLCF_F_TPT exchanges the loss: avg_entropy of the selected views (tpt.hip) where the reward loss or a distillation loss stood;
-// selection, backward, step skip and AdamW are the RL path's.  No reward pass, no teacher, no top-K stage: an engine without a
-// reward model serves it.
-int engine_tpt_check(const rlcf_tta_args* a, const char* entry) {
-    if (!tpt_on(a)) return RLCF_OK;
-    if (a->flags & (RLCF_F_KD_MASK | RLCF_F_MIN_ENTROPY | RLCF_F_NO_SELECTION)) {
-        rlcf_set_error("%s: the TPT loss (RLCF_F_TPT) takes no distillation loss, no min-entropy regulariser and no retrieval rows (flags 0x%x)",
-                       entry, a->flags);
+// ------------------------------------------------------------------ what every tuning entry shares: the check, the loss, the optimizer
+// One rule set for all entries (api.hip calls it once per call, before anything is launched; the engine functions below trust it).
+// kinds: LOSS_BIT()s of the losses the entry has a form of; what: TTA_* traits.  RLCF_ERR_ARG for what the arguments ask, RLCF_ERR_STATE
+// for what the engine lacks; the argument rules come first.
+int tta_args_check(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry, unsigned kinds, unsigned what) {
+    static const char* const name[] = {"the reward loss", "the distillation loss RLCF_F_KD", "the distillation loss RLCF_F_DKD",
+                                       "the distillation loss RLCF_F_ATKD", "the TPT loss RLCF_F_TPT"};
+    LossKind k = loss_kind(a);
+    if ((what & TTA_DISTILS) && k == LOSS_RL) k = LOSS_KD;
+    if (!(kinds & LOSS_BIT(k))) {
+        // tune_cls_kd.py has no prompt, batched, lane or policy form, clip_ret_kd.py no DKD / ATKD form; TPT/tpt_cls.py and tune_cls_tpt.py
+        // have no lane and no retrieval form
+        rlcf_set_error("%s: %s has no form on this entry (the distillation losses RLCF_F_KD / RLCF_F_DKD / RLCF_F_ATKD run on rlcf_tta_sample_ln / "
+                       "rlcf_tta_sample_visual, kd_distill_loss_v2 alone on the two retrieval *_kd entries; RLCF_F_TPT on rlcf_tta_sample / "
+                       "rlcf_tta_sample_ln / rlcf_tta_sample_visual / rlcf_tta_batch / rlcf_tta_batch_ln)", entry, name[k]);
+        return RLCF_ERR_ARG;
+    }
+    if (k != LOSS_RL) {
+        const int refused = RLCF_F_MIN_ENTROPY | (k == LOSS_TPT ? RLCF_F_KD_MASK : 0) | ((what & TTA_ROWS_IN_ORDER) ? 0 : RLCF_F_NO_SELECTION);
+        if (a->flags & refused) {
+            rlcf_set_error("%s: %s takes no second loss, no min-entropy regulariser and no retrieval rows (flags 0x%x)", entry, name[k], a->flags);
+            return RLCF_ERR_ARG;
+        }
+    }
+    if (loss_distils(k) && e->n_rewards != 1) {      // CLIPRewardsMultiple has no calulate_similarity (clip_reward.py:180-307)
+        rlcf_set_error("%s: the distillation losses need exactly one reward model (the engine holds %d)", entry, e->n_rewards);
+        return RLCF_ERR_ARG;
+    }
+    const bool image_bank = (what & TTA_IMAGE_BANK) != 0;
+    if (e->C <= 0 || e->image_bank != image_bank || (e->n_rewards <= 0 && k != LOSS_TPT)) {      // (the TPT loss needs no reward model)
+        rlcf_set_error("%s: %s bank / reward model not set", entry, image_bank ? "image" : "class");
+        return RLCF_ERR_STATE;
+    }
+    if ((what & TTA_PROMPT) && e->n_ctx <= 0) {
+        rlcf_set_error("%s: prompt tuning needs a class bank with learnable context rows (n_ctx > 0)", entry);
+        return RLCF_ERR_STATE;
+    }
+    if (k == LOSS_RL && !(a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C)) {        // (only the reward loss samples classes)
+        rlcf_set_error("%s: sample_k = %d (need 1 <= sample_k <= 32 and <= the bank's %d entries)", entry, a->sample_k, e->C);
         return RLCF_ERR_ARG;
     }
     return RLCF_OK;
 }
-// what every tuning entry asks of the engine's state and of sample_k (ignored under RLCF_F_TPT, which needs no reward model either)
-static int tta_state_check(const rlcf_engine* e, const rlcf_tta_args* a) {
-    if (e->C <= 0 || e->image_bank || (e->n_rewards <= 0 && !tpt_on(a))) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
+
+#define COPY_OUT(dst, src, bytes) do { if (dst) RLCF_HIP_CHECK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st)); } while (0)
+// out[0] = sum_i a[i] * b[i]  (one block, fixed reduction order)
+__global__ void dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out) {
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) acc += a[i] * b[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+// The loss of one step over `groups` samples of n_sel rows of e->sel_logits: dlogits into e->dlogits, the loss [groups] into loss_out
+// (optional), and for the reward loss the sampled classes into e->topk_idx (with loss_out: their e->clip_score / e->rewards too).
+//   LOSS_RL   top-K sampling, CLIP reward, baseline, reward-weighted CE (tpt_cls_rl.py:63-74)
+//   LOSS_KD / DKD / ATKD  against e->kd_teacher (tune_cls_kd.py:48-55).  rkd != NULL: the retrieval form, kd_distill_loss_v2 with these
+//             temperatures over rows as long as the bank (clip_ret_kd.py:62,87); the split-row kernels take over from the
+//             one-workgroup-per-row kernel where they are faster (profiles/retrieval_kd_notes.md) — a choice by C alone, so a given
+//             query computes the same bits on every device
+//   LOSS_TPT  avg_entropy of each sample's rows (tpt_cls.py:49-72); no reward pass, no teacher, no top-K stage
+// dot (optional, one row) = <dlogits, sel_logits>, one float.
+static int loss_step(rlcf_engine* e, const rlcf_tta_args* a, LossKind kind, int groups, int n_sel, const rlcf_kd_params* rkd, float* dot,
+                     float* loss_out, hipStream_t st) {
+    const int C = e->C;
+    const float* rows = e->sel_logits.as<float>();
+    float* dlogits = e->dlogits.as<float>();
+    if (kind == LOSS_RL) {
+        TRY(launch_reward_loss_bank(rows, C, nullptr, groups, n_sel, C, a->sample_k, reward_bank(e), a->clipscore_weight, a->flags,
+                                    a->min_entropy_w, e->topk_idx.as<int32_t>(), loss_out ? e->clip_score.as<float>() : nullptr,
+                                    loss_out ? e->rewards.as<float>() : nullptr, loss_out, dlogits, e->rl_stats.as<float>(), st));
+    } else if (kind == LOSS_TPT) {
+        TRY(e->loss_ws.ensure(tpt_ws_bytes(groups, n_sel, C)));
+        TRY(launch_tpt_loss(rows, C, groups, n_sel, C, loss_out, dlogits, e->loss_ws.as<double>(), st));
+    } else if (rkd && C >= KD_SPLIT_MIN_C) {     // (this kernel hands the dot product over with the gradient row)
+        TRY(e->loss_ws.ensure(kd_split_ws_bytes(n_sel, C)));
+        return launch_kd_loss_split(rows, C, e->kd_teacher.as<float>(), C, n_sel, C, rkd, loss_out, nullptr, dlogits, dot, e->loss_ws.as<double>(), st);
+    } else {
+        TRY(e->loss_ws.ensure((size_t)n_sel * sizeof(double)));
+        TRY(launch_kd_loss(rows, C, e->kd_teacher.as<float>(), C, n_sel, C, kind, nullptr, rkd, loss_out, nullptr, dlogits, e->loss_ws.as<double>(), st));
+    }
+    if (dot) {
+        RLCF_ARG_CHECK(groups * n_sel == 1);
+        dot_kernel<<<dim3(1), dim3(256), 0, st>>>(dlogits, rows, C, dot);
+        RLCF_LAUNCH_CHECK();
+    }
     return RLCF_OK;
 }
-static bool sample_k_ok(const rlcf_engine* e, const rlcf_tta_args* a) {
-    return tpt_on(a) || (a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+// what the first step's loss leaves for the caller (rows = the rows of dlogits, n_e = the sampled (row, class) pairs).  The distillation
+// and TPT losses sample no classes: topk_idx / clip_score / rewards stay unwritten.
+static int loss_copy_out(rlcf_engine* e, const rlcf_tta_out* out, LossKind kind, int rows, int n_e, hipStream_t st) {
+    if (kind == LOSS_RL) {
+        COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
+        COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
+        COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
+    }
+    COPY_OUT(out->loss, e->loss.p, sizeof(float));
+    COPY_OUT(out->dlogits, e->dlogits.p, (size_t)rows * e->C * sizeof(float));
+    return RLCF_OK;
 }
-// loss [groups] (optional) and dlogits of `groups` samples of n_sel rows of e->sel_logits, where the reward loss leaves them
-static int tpt_step(rlcf_engine* e, int groups, int n_sel, float* loss, hipStream_t st) {
-    TRY(e->tpt_ws.ensure(tpt_ws_bytes(groups, n_sel, e->C)));
-    return launch_tpt_loss(e->sel_logits.as<float>(), e->C, groups, n_sel, e->C, loss, e->dlogits.as<float>(), (double*)e->tpt_ws.p, st);
+// scaler.step(optimizer) (tpt_cls_rl.py:78) as AdamW step j + 1 over one or two buffers of one optimizer, `sets` parameter sets each (one
+// per test sample of a fused batch): a gradient with an inf / NaN anywhere in a set's buffers skips that set's update (the same inputs
+// give the same gradient at the following steps, so the host-side step number never meets an applied step after a skipped one).
+// Derived weight forms are the caller's to refresh.
+struct OptimBuf { float *params; const float* grad; float *m, *v; int64_t count; };      // count: floats of one set
+static int optim_step(rlcf_engine* e, const rlcf_tta_args* a, int j, const OptimBuf* bufs, int n_bufs, int sets, int32_t* step_skipped_out,
+                      hipStream_t st) {
+    int32_t* skip = e->step_skip.as<int32_t>();
+    for (int i = 0; i < n_bufs; ++i) TRY(launch_grad_nonfinite(bufs[i].grad, bufs[i].count, sets, skip, st, i > 0));
+    if (step_skipped_out) COPY_OUT(step_skipped_out + j, skip, sizeof(int32_t));
+    for (int i = 0; i < n_bufs; ++i)
+        TRY(launch_adamw(bufs[i].params, bufs[i].grad, bufs[i].m, bufs[i].v, sets * bufs[i].count, j + 1, a->lr, a->beta1, a->beta2, a->eps,
+                         a->weight_decay, st, skip, bufs[i].count));
+    return RLCF_OK;
 }
 
 // Harness body TPT/tpt_cls_rl.py:251-262 around test_time_tuning (:47-79).
-#define COPY_OUT(dst, src, bytes) do { if (dst) RLCF_HIP_CHECK(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st)); } while (0)
 int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    RLCF_ARG_CHECK(a);
-    TRY(tta_state_check(e, a));
-    if (e->n_ctx <= 0) { rlcf_set_error("prompt tuning needs a class bank with learnable context rows (n_ctx > 0)"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->tta_steps >= 0 && sample_k_ok(e, a));
-    TRY(engine_tpt_check(a, "rlcf_tta_sample"));
-    const bool tpt = tpt_on(a);
-    const int C = e->C, K = tpt ? 1 : a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, n_ctx = e->n_ctx;
+    RLCF_ARG_CHECK(a && N > 0 && N <= e->max_views && a->tta_steps >= 0);
+    const LossKind kind = loss_kind(a);
+    const int C = e->C, K = kind == LOSS_TPT ? 1 : a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, n_ctx = e->n_ctx;
     const int n_sel = n_selected(a, N);                       // int() truncation, tpt_cls_rl.py:34
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
     const size_t cb = (size_t)n_ctx * Wt * sizeof(float);
@@ -135,7 +224,7 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
     const rlcf_tta_out none{};
     if (!out) out = &none;
     const bool sparse_ok = a->sparse_backward && (a->flags & RLCF_F_REWARD_PROCESS) && !(a->flags & RLCF_F_PROCESS_BATCH) &&
-                           !(a->flags & RLCF_F_MIN_ENTROPY) && K > 1 && !tpt;      // (the TPT loss is dense over the classes)
+                           !(a->flags & RLCF_F_MIN_ENTROPY) && K > 1 && kind == LOSS_RL;      // (the TPT loss is dense over the classes)
     const int n_e = n_sel * K;
     if (a->tta_steps > 0) {
         if (sparse_ok) TRY(sparse_ensure(e, n_e, st));
@@ -166,7 +255,6 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
         const bool cached = (j == 0 && sparse_ok && !a->ctx_in);
         if (!cached) TRY(text_forward(e, s, e->lay[0], e->tt, ctx, io, !sparse_ok, st));
         const float* txt_j = cached ? e->txt0.as<float>() : e->txt.as<float>();
-        const float* rows_logits;
         if (j == 0) {   // tpt_cls_rl.py:57-59
             TRY(engine_logits(e, e->img_feat.as<float>(), N, txt_j, C, e->logits.as<float>(), st));
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
@@ -194,15 +282,14 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
                     if (er != hipSuccess) { (void)hipStreamSynchronize(e->side); rlcf_set_error("hipEventRecord(ev_join): %s", hipGetErrorString(er)); return RLCF_ERR_HIP; }
                     return rc_side;
                 }
-            } else if (!tpt) {
+            } else if (kind != LOSS_TPT) {
                 TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
             }
             TRY(launch_gather_rows(e->logits.as<float>(), C, e->sel_idx.as<int32_t>(), e->sel_logits.as<float>(), C, n_sel, C, st));
-            rows_logits = e->sel_logits.as<float>();
             if (overlap) {
                 // whatever happens on the main stream, it joins the side stream before this call returns: the side stream writes
                 // e->vt, e->rimg and the caller's reward_image_features
-                int rc_main = launch_topk_rows(rows_logits, C, n_sel, C, K, e->topk_idx.as<int32_t>(), e->rl_stats.as<float>(), st);
+                int rc_main = launch_topk_rows(e->sel_logits.as<float>(), C, n_sel, C, K, e->topk_idx.as<int32_t>(), e->rl_stats.as<float>(), st);
                 if (rc_main == RLCF_OK) rc_main = sparse_forward(e, ctx, e->topk_idx.as<int32_t>(), n_e, st);
                 fwd_done = true;
                 const hipError_t ej = hipStreamWaitEvent(st, e->ev_join, 0);
@@ -214,12 +301,8 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
             COPY_OUT(out->selected_idx, e->sel_idx.p, n_sel * sizeof(int32_t));
         } else {        // tpt_cls_rl.py:55 — selected views only; their image features are unchanged
             TRY(engine_logits(e, e->sel_feat.as<float>(), n_sel, txt_j, C, e->sel_logits.as<float>(), st));
-            rows_logits = e->sel_logits.as<float>();
         }
-        if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));         // (rows_logits is e->sel_logits at every step)
-        else TRY(launch_reward_loss_bank(rows_logits, C, nullptr, 1, n_sel, C, K, reward_bank(e),
-                               a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
-                               e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
+        TRY(loss_step(e, a, kind, 1, n_sel, nullptr, nullptr, e->loss.as<float>(), st));
         if (sparse_ok && fwd_done) {
             TRY(sparse_backward_only(e, e->sel_feat.as<float>(), e->topk_idx.as<int32_t>(), n_e, K, e->dlogits.as<float>(), e->ctx_grad.as<float>(), st));
             fwd_done = false;
@@ -232,21 +315,11 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
                               e->lay[0].ctx_rows_list.as<int32_t>(), e->lay[0].n_copies, n_ctx, e->ctx_grad.as<float>(), st));
         }
         if (j == 0) {
-            if (!tpt) {          // (the TPT loss samples no classes: topk_idx / clip_score / rewards stay unwritten)
-                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
-            }
-            COPY_OUT(out->loss, e->loss.p, sizeof(float));
-            COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
+            TRY(loss_copy_out(e, out, kind, n_sel, n_e, st));
             COPY_OUT(out->ctx_grad, e->ctx_grad.p, cb);
         }
-        // scaler.step(optimizer) (tpt_cls_rl.py:78): a gradient with an inf / NaN skips the update (the same inputs give the same
-        // gradient at the following steps, so the host-side step number j + 1 never meets an applied step after a skipped one)
-        TRY(launch_grad_nonfinite(e->ctx_grad.as<float>(), (int64_t)n_ctx * Wt, 1, e->step_skip.as<int32_t>(), st));
-        TRY(launch_adamw(ctx, e->ctx_grad.as<float>(), e->adam_m.as<float>(), e->adam_v.as<float>(), (int64_t)n_ctx * Wt, j + 1, a->lr,
-                         a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), (int64_t)n_ctx * Wt));
-        if (out->step_skipped) COPY_OUT(out->step_skipped + j, e->step_skip.p, sizeof(int32_t));
+        const OptimBuf ob{ctx, e->ctx_grad.as<float>(), e->adam_m.as<float>(), e->adam_v.as<float>(), (int64_t)n_ctx * Wt};
+        TRY(optim_step(e, a, j, &ob, 1, 1, out->step_skipped, st));
     }
     // final inference on the clean view (views[0]) with the adapted prompt, tpt_cls_rl.py:260-262;
     // its image feature is row 0 of img_feat (frozen image tower: identical to re-encoding it).
@@ -339,9 +412,7 @@ static int tta_batch_fused(rlcf_engine* e, const float* views, int B, int N, con
             e->last_flops += 2.0 * BS * C * D;
         }
         // 3. top-K sampling, CLIP reward, baseline, reward-weighted CE and dlogits, grouped per sample
-        TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, B, n_sel, C, K, reward_bank(e),
-                                    a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), nullptr, nullptr, nullptr,
-                                    e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
+        TRY(loss_step(e, a, LOSS_RL, B, n_sel, nullptr, nullptr, nullptr, st));
         // 4. sparse backward of all B*n_e sampled (view, class) pairs; each sample owns a copy of the prompt prefix
         TRY(launch_build_sparse_layout(e->topk_idx.as<int32_t>(), B, n_e, L.class_start.as<int32_t>(), L.class_len.as<int32_t>(),
                                        L.class_eot_off.as<int32_t>(), L.lmax, L.pre_rows, e->sp_seqs.as<rlcf_seq>(), e->sp_eot_rows.as<int32_t>(),
@@ -370,9 +441,8 @@ static int tta_batch_fused(rlcf_engine* e, const float* views, int B, int N, con
                                             e->b_grad.as<float>(), st));
         }
         // 5. AdamW step j+1 of every sample (tpt_cls_rl.py:76-79)
-        TRY(launch_grad_nonfinite(e->b_grad.as<float>(), np, B, e->step_skip.as<int32_t>(), st));
-        TRY(launch_adamw(e->b_ctx.as<float>(), e->b_grad.as<float>(), e->b_m.as<float>(), e->b_v.as<float>(), B * np, j + 1, a->lr, a->beta1,
-                         a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), np));
+        const OptimBuf ob{e->b_ctx.as<float>(), e->b_grad.as<float>(), e->b_m.as<float>(), e->b_v.as<float>(), np};
+        TRY(optim_step(e, a, j, &ob, 1, B, nullptr, st));
     }
     // 6. final clean-view inference: B adapted prompts through one replicated text pass
     TRY(text_forward(e, s, L, e->tt, e->b_ctx.as<float>(), fo, false, st));
@@ -434,14 +504,11 @@ static int tta_batch_pipelined(rlcf_engine* e, const float* views, int B, int N,
 int engine_tta_batch(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                      hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    TRY(tta_state_check(e, a));
-    if (e->n_ctx <= 0) { rlcf_set_error("prompt tuning needs a class bank with learnable context rows (n_ctx > 0)"); return RLCF_ERR_STATE; }
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && sample_k_ok(e, a));
-    TRY(engine_tpt_check(a, "rlcf_tta_batch"));
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views);
     const size_t per = (size_t)N * 3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const int n_sel = n_selected(a, N);
     const bool sparse_ok = a->sparse_backward && (a->flags & RLCF_F_REWARD_PROCESS) && !(a->flags & RLCF_F_PROCESS_BATCH) &&
-                           !(a->flags & RLCF_F_MIN_ENTROPY) && a->sample_k > 1 && !tpt_on(a);      // (RLCF_F_TPT: dense backward, sample by sample)
+                           !(a->flags & RLCF_F_MIN_ENTROPY) && a->sample_k > 1 && loss_kind(a) == LOSS_RL;      // (RLCF_F_TPT: dense backward, sample by sample)
     const int Bmax = e->max_views / N;
     const bool fused = Bmax >= 2 && a->tta_steps >= 1 && sparse_ok && !a->ctx_in && !a->skip_final && n_sel > 0;
     double flops = 0.0;

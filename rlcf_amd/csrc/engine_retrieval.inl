@@ -86,7 +86,6 @@ __global__ void scale_by_exp_kernel(float* __restrict__ x, const float* __restri
     const float s = expf(*log_scale);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] *= s;
 }
-// (dot_kernel, out[0] = sum_i a[i] * b[i]: engine_tuning.inl, next to the distillation loss that also uses it)
 // embedding gradients of one packed text: x[r] = token_embedding[token[r]] + positional_embedding[pos[r]] (model.py:344-346), so
 // d positional_embedding[pos[r]] += dX[r], d token_embedding[token[r]] += dX[r].  One thread per column walks the rows in order:
 // repeated tokens accumulate in a fixed order, no atomics.
@@ -156,11 +155,9 @@ static int rebuild_E(ClipModel& m, TextLayout& L, hipStream_t st) {
 int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st,
                               const rlcf_kd_params* kd) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    if (kd) TRY(engine_kd_refusals(e, a, "rlcf_tta_retrieval_text_kd"));
-    if (e->C <= 0 || !e->image_bank || e->n_rewards <= 0) { rlcf_set_error("image bank / reward model not set"); return RLCF_ERR_STATE; }
     RLCF_ARG_CHECK(tokens && a && a->tta_steps >= 0);
     if (kd) RLCF_ARG_CHECK(kd->T_stu > 0.f && kd->T_tea > 0.f);
-    else RLCF_ARG_CHECK(a->sample_k > 0 && a->sample_k <= 32 && a->sample_k <= e->C);
+    const LossKind kind = kd ? LOSS_KD : LOSS_RL;
     TRY(engine_text_enable(e, st));
     const int C = e->C, K = kd ? 1 : a->sample_k, D = s.cfg.embed_dim, Wt = s.cfg.text_width, L = s.cfg.text_layers;
     const rlcf_tta_out none{};
@@ -218,18 +215,10 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
     for (int j = 0; j < a->tta_steps; ++j) {
         TRY(text_forward(e, s, Q, e->st, nullptr, io, true, st));
         TRY(logits_per_text(e->sel_logits.as<float>()));
-        if (!kd) TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, 1, C, K, reward_bank(e), a->clipscore_weight, a->flags,
-                                             a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(), e->rewards.as<float>(),
-                                             e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
         RLCF_HIP_CHECK(hipMemsetAsync(G, 0, wb, st));
         RLCF_HIP_CHECK(hipMemsetAsync(GL, 0, lb, st));
         // logits = exp(logit_scale) * <feat, bank>:  d logit_scale = <dlogits, logits>,  d feat = exp(logit_scale) * dlogits @ bank
-        if (kd) {              // (the loss kernels hand the dot product over with the gradient row)
-            TRY(kd_retrieval_loss(e, e->sel_logits.as<float>(), 1, kd, G + e->tw_slots.back().off, st));
-        } else {
-            dot_kernel<<<dim3(1), dim3(256), 0, st>>>(e->dlogits.as<float>(), e->sel_logits.as<float>(), C, G + e->tw_slots.back().off);
-            RLCF_LAUNCH_CHECK();
-        }
+        TRY(loss_step(e, a, kind, 1, 1, kd, G + e->tw_slots.back().off, e->loss.as<float>(), st));
         TRY(launch_dimg(e->dlogits.as<float>(), e->txt0.as<float>(), 1, C, D, 1.0f, e->q_dfeat.as<float>(), st));
         scale_by_exp_kernel<<<dim3(1), dim3(256), 0, st>>>(e->q_dfeat.as<float>(), ls, D);
         RLCF_LAUNCH_CHECK();
@@ -247,24 +236,14 @@ int engine_tta_retrieval_text(rlcf_engine* e, const int32_t* tokens, const rlcf_
         RLCF_LAUNCH_CHECK();
         if (j == 0) {
             COPY_OUT(out->logits, e->sel_logits.p, (size_t)C * sizeof(float));
-            if (!kd) {
-                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)K * sizeof(int32_t));
-                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)K * sizeof(float));
-                COPY_OUT(out->rewards, e->rewards.p, (size_t)K * sizeof(float));
-            }
-            COPY_OUT(out->loss, e->loss.p, sizeof(float));
-            COPY_OUT(out->dlogits, e->dlogits.p, (size_t)C * sizeof(float));
+            TRY(loss_copy_out(e, out, kind, 1, K, st));
             COPY_OUT(out->vis_grad, G, wb);
             COPY_OUT(out->ln_grad, GL, lb);
             COPY_OUT(out->reward_image_features, e->rimg[0].p, (size_t)e->model[RLCF_REWARD].cfg.embed_dim * sizeof(float));
         }
-        TRY(launch_grad_nonfinite(GL, e->tln_count, 1, e->step_skip.as<int32_t>(), st));
-        TRY(launch_grad_nonfinite(G, (int64_t)e->tw_count, 1, e->step_skip.as<int32_t>(), st, true));
-        if (out->step_skipped) COPY_OUT(out->step_skipped + j, e->step_skip.p, sizeof(int32_t));
-        TRY(launch_adamw(e->tln.as<float>(), GL, e->tln_m.as<float>(), e->tln_v.as<float>(), e->tln_count, j + 1, a->lr, a->beta1, a->beta2,
-                         a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), e->tln_count));
-        TRY(launch_adamw(e->tw.as<float>(), G, e->tw_m.as<float>(), e->tw_v.as<float>(), (int64_t)e->tw_count, j + 1, a->lr, a->beta1, a->beta2,
-                         a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), (int64_t)e->tw_count));
+        const OptimBuf ob[2] = {{e->tln.as<float>(), GL, e->tln_m.as<float>(), e->tln_v.as<float>(), e->tln_count},
+                                {e->tw.as<float>(), G, e->tw_m.as<float>(), e->tw_v.as<float>(), (int64_t)e->tw_count}};
+        TRY(optim_step(e, a, j, ob, 2, 1, out->step_skipped, st));
         e->tw_dirty = true;
         TRY(refresh_derived(e->tw_refresh, 0, st));
         TRY(rebuild_E(s, Q, st));

@@ -78,8 +78,8 @@ static int vit_backward_ln(rlcf_engine* e, ClipModel& m, const float* feats, int
 static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                               hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    const bool tpt = tpt_on(a);
-    const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
+    const LossKind kind = loss_kind(a);
+    const int C = e->C, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), BN = B * N, BS = B * n_sel;
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const size_t nb = (size_t)e->ln_count * sizeof(float), np = (size_t)e->ln_count;
@@ -94,7 +94,7 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
     TRY(engine_logits(e, e->img_feat.as<float>(), BN, cls_feat, C, e->logits.as<float>(), st));
     TRY(launch_entropy_select_batched(e->logits.as<float>(), B, N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
     TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, BS, (int)img_elems, st));
-    if (!tpt) TRY(reward_encode(e, BS, s.cfg.image_resolution, nullptr, st));
+    if (kind != LOSS_TPT) TRY(reward_encode(e, BS, s.cfg.image_resolution, nullptr, st));
     // reset state of every sample (custom_clip.py:456-458 + optimizer.load_state_dict)
     TRY(launch_broadcast_rows(e->ln_init.as<float>(), e->b_ln.as<float>(), (int)np, B, st));
     RLCF_HIP_CHECK(hipMemsetAsync(e->b_ln_m.p, 0, B * nb, st));
@@ -105,16 +105,12 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
         e->lng_base = e->b_ln.as<float>(); e->lng_views = n_sel;
         int rc = vit_forward_saved(e, s, e->views_sel.as<float>(), BS, e->ln_feat.as<float>(), st);
         if (rc == RLCF_OK) rc = engine_logits(e, e->ln_feat.as<float>(), BS, cls_feat, C, e->sel_logits.as<float>(), st);
-        if (rc == RLCF_OK && tpt) rc = tpt_step(e, B, n_sel, nullptr, st);          // one group per sample
-        else if (rc == RLCF_OK) rc = launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, B, n_sel, C, K, reward_bank(e), a->clipscore_weight,
-                                                        a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), nullptr, nullptr, nullptr,
-                                                        e->dlogits.as<float>(), e->rl_stats.as<float>(), st);
+        if (rc == RLCF_OK) rc = loss_step(e, a, kind, B, n_sel, nullptr, nullptr, nullptr, st);          // one group per sample
         if (rc == RLCF_OK) rc = vit_backward_ln(e, s, e->ln_feat.as<float>(), BS, e->dlogits.as<float>(), e->b_ln_grad.as<float>(), st, B);
         e->lng_base = nullptr; e->lng_views = 1;
         TRY(rc);
-        TRY(launch_grad_nonfinite(e->b_ln_grad.as<float>(), (int64_t)np, B, e->step_skip.as<int32_t>(), st));
-        TRY(launch_adamw(e->b_ln.as<float>(), e->b_ln_grad.as<float>(), e->b_ln_m.as<float>(), e->b_ln_v.as<float>(), (int64_t)B * np, j + 1,
-                         a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), (int64_t)np));
+        const OptimBuf ob{e->b_ln.as<float>(), e->b_ln_grad.as<float>(), e->b_ln_m.as<float>(), e->b_ln_v.as<float>(), (int64_t)np};
+        TRY(optim_step(e, a, j, &ob, 1, B, nullptr, st));
     }
     // 6. clean-view inference of the B samples in one pass: view b reads LayerNorm set b (tune_cls_rl.py:219-221)
     float* fl = final_logits ? final_logits : e->b_logits.as<float>();
@@ -133,9 +129,7 @@ static int tta_batch_ln_fused(rlcf_engine* e, const float* views, int B, int N, 
 int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, const rlcf_tta_args* a, float* final_logits, int32_t* top5,
                         hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    TRY(tta_state_check(e, a));
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && sample_k_ok(e, a));
-    TRY(engine_tpt_check(a, "rlcf_tta_batch_ln"));
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views);
     const bool rn = is_resnet(s.cfg);         // BatchNorm tuning: the batch statistics couple one sample's views, samples run one by one
     RLCF_ARG_CHECK(rn || s.tokens <= 320);
     const size_t per = (size_t)N * 3 * s.cfg.image_resolution * s.cfg.image_resolution;
@@ -163,20 +157,6 @@ int engine_tta_batch_ln(rlcf_engine* e, const float* views, int count, int N, co
 // ------------------------------------------------------------------ distillation losses (TPT/tune_cls_kd.py:34-61)
 // The KD ablation adapts the same student with the same frozen CLIP, the reward loss replaced by a distillation loss against the
 // reward model's logits of the selected views; selection, backward, step skip and AdamW are the RL path's.
-static int kd_mode(const rlcf_tta_args* a) { return (a->flags & RLCF_F_KD_MASK) >> 5; }
-// retrieval: the caller is rlcf_tta_retrieval_image_kd, the one entry that distils over rows taken in order
-static int kd_check(const rlcf_engine* e, const rlcf_tta_args* a, bool retrieval = false) {
-    if (!kd_mode(a)) return RLCF_OK;
-    if (a->flags & (RLCF_F_MIN_ENTROPY | (retrieval ? 0 : RLCF_F_NO_SELECTION))) {
-        rlcf_set_error("the distillation losses take no min-entropy regulariser and no retrieval rows (flags 0x%x)", a->flags);
-        return RLCF_ERR_ARG;
-    }
-    if (e->n_rewards != 1) {        // CLIPRewardsMultiple has no calulate_similarity (clip_reward.py:180-307): KD needs one reward model
-        rlcf_set_error("the distillation losses need exactly one reward model (the engine holds %d)", e->n_rewards);
-        return RLCF_ERR_ARG;
-    }
-    return RLCF_OK;
-}
 // reward_model.calulate_similarity() on the selected views (tune_cls_kd.py:45-46, clip_reward.py:168-177):
 // r_logits_per_image = exp(reward.logit_scale) * reward_image_features @ reward_class_features^T, computed once at step 0
 static int kd_teacher(rlcf_engine* e, int n_sel, hipStream_t st) {
@@ -186,47 +166,6 @@ static int kd_teacher(rlcf_engine* e, int n_sel, hipStream_t st) {
     e->kd_teacher_rows = n_sel; e->kd_teacher_C = C;
     return gemm(e, e->rimg[0].as<float>(), Dr, e->reward_cls[0].as<float>(), Dr, nullptr, nullptr, 0, nullptr, 0, e->kd_teacher.as<float>(), C,
                 n_sel, C, Dr, r.logit_scale_exp, RLCF_EPI_NONE, st);
-}
-// loss and dlogits of one step (tune_cls_kd.py:48-55) into e->loss / e->dlogits, where the reward loss leaves them
-// retrieval (retrieval/clip_ret_kd.py:62,87): kd_distill_loss_v2 over one or a few rows as long as the bank.  The split-row kernels
-// take over from the one-workgroup-per-row kernel where they are faster (profiles/retrieval_kd_notes.md); the choice depends on
-// (n, C) only, so a given query computes the same bits on every device.  dot (optional) = <dlogits, student>, one float.
-// out[0] = sum_i a[i] * b[i]  (one block, fixed reduction order)
-__global__ void dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += a[i] * b[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
-static bool kd_split_wins(int n, int C) { return C >= KD_SPLIT_MIN_C; }
-static int kd_retrieval_loss(rlcf_engine* e, const float* student, int n, const rlcf_kd_params* kdp, float* dot, hipStream_t st) {
-    const int C = e->C;
-    if (kd_split_wins(n, C)) {
-        TRY(e->kd_ws.ensure(kd_split_ws_bytes(n, C)));
-        return launch_kd_loss_split(student, C, e->kd_teacher.as<float>(), C, n, C, kdp, e->loss.as<float>(), nullptr, e->dlogits.as<float>(),
-                                    dot, (double*)e->kd_ws.p, st);
-    }
-    TRY(e->kd_ws.ensure((size_t)n * sizeof(double)));
-    TRY(launch_kd_loss(student, C, e->kd_teacher.as<float>(), C, n, C, RLCF_KD_KD, nullptr, kdp, e->loss.as<float>(), nullptr,
-                       e->dlogits.as<float>(), (double*)e->kd_ws.p, st));
-    if (dot) {
-        RLCF_ARG_CHECK(n == 1);
-        dot_kernel<<<dim3(1), dim3(256), 0, st>>>(e->dlogits.as<float>(), student, C, dot);
-        RLCF_LAUNCH_CHECK();
-    }
-    return RLCF_OK;
-}
-// rkd != NULL: the retrieval form (rlcf_tta_retrieval_image_kd), kd_distill_loss_v2 with its temperatures over rows as long as the bank
-static int kd_step(rlcf_engine* e, int n_sel, const rlcf_tta_args* a, hipStream_t st, const rlcf_kd_params* rkd = nullptr) {
-    if (rkd) return kd_retrieval_loss(e, e->sel_logits.as<float>(), n_sel, rkd, nullptr, st);
-    return launch_kd_loss(e->sel_logits.as<float>(), e->C, e->kd_teacher.as<float>(), e->C, n_sel, e->C, kd_mode(a), nullptr, nullptr,
-                          e->loss.as<float>(), nullptr, e->dlogits.as<float>(), (double*)e->rl_stats.p, st);
 }
 
 // ------------------------------------------------------------------ BatchNorm tuning of a ModifiedResNet student
@@ -238,11 +177,17 @@ static int kd_step(rlcf_engine* e, int n_sel, const rlcf_tta_args* a, hipStream_
 // CLIPCLS_TTA.train() (custom_clip.py:487-497) puts the norm layers in train mode whatever `mode` is, so the final clean-view
 // inference ALSO normalises with batch statistics (of that one image): reproduced.  The running statistics the sample leaves behind
 // stay in e->bn_stats (rlcf_engine_get_bn_stats) until the next sample resets them.
-static int rn_visual_reset(rlcf_engine* e, hipStream_t st) {   // visual.load_state_dict(initial_state_dict) for the flat buffer of a ResNet student
+static int visual_reset(rlcf_engine* e, hipStream_t st) {      // visual.load_state_dict(initial_state_dict) for the flat buffer (ViT or ResNet student)
     if (!e->vw_count || !e->vw_dirty) return RLCF_OK;
     RLCF_HIP_CHECK(hipMemcpyAsync(e->vw.p, e->vw_init.p, e->vw_count * sizeof(float), hipMemcpyDeviceToDevice, st));
     e->vw_dirty = false;
-    return rn_visual_refresh(e, st, e->vw_init_is_ckpt);
+    return is_resnet(e->model[RLCF_STUDENT].cfg) ? rn_visual_refresh(e, st, e->vw_init_is_ckpt) : engine_visual_refresh(e, st, e->vw_init_is_ckpt);
+}
+// one optimizer over the norm-layer buffer and (full) the flat buffer of every other visual parameter
+static int visual_optim_step(rlcf_engine* e, const rlcf_tta_args* a, int j, bool full, int32_t* step_skipped_out, hipStream_t st) {
+    const OptimBuf ob[2] = {{e->ln_params.as<float>(), e->ln_grad.as<float>(), e->ln_m.as<float>(), e->ln_v.as<float>(), e->ln_count},
+                            {e->vw.as<float>(), e->vw_grad.as<float>(), e->vw_m.as<float>(), e->vw_v.as<float>(), (int64_t)e->vw_count}};
+    return optim_step(e, a, j, ob, full ? 2 : 1, 1, step_skipped_out, st);
 }
 // full: every visual parameter is tuned (CLIPCLS_TTA(only_norm=False) on a ModifiedResNet — the parser defaults of tune_cls_rl.py,
 // TPT/params.py:23,73): convolution / downsample.1 / attention-pool gradients into e->vw_grad, a second AdamW launch, the derived
@@ -252,11 +197,11 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
     ClipModel& s = e->model[RLCF_STUDENT];
     TRY(engine_bn_enable(e, st));
     if (full) TRY(engine_rn_visual_enable(e, st));
-    if (!full && s.rn.full_enabled && e->vw_dirty) TRY(rn_visual_reset(e, st));
+    if (!full && s.rn.full_enabled && e->vw_dirty) TRY(visual_reset(e, st));
     const size_t vb = full ? e->vw_count * sizeof(float) : 0;
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
-    const bool kd = kd_mode(a) != 0, tpt = tpt_on(a);
+    const LossKind kind = loss_kind(a);
     const size_t img_elems = (size_t)3 * s.cfg.image_resolution * s.cfg.image_resolution;
     const size_t nb = (size_t)e->ln_count * sizeof(float);
     const rlcf_tta_out none{};
@@ -271,7 +216,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
     RLCF_HIP_CHECK(hipMemsetAsync(e->ln_m.p, 0, nb, st));
     RLCF_HIP_CHECK(hipMemsetAsync(e->ln_v.p, 0, nb, st));
     if (full) {
-        TRY(rn_visual_reset(e, st));
+        TRY(visual_reset(e, st));
         RLCF_HIP_CHECK(hipMemsetAsync(e->vw_m.p, 0, vb, st));
         RLCF_HIP_CHECK(hipMemsetAsync(e->vw_v.p, 0, vb, st));
     }
@@ -284,8 +229,8 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
             TRY(engine_logits(e, e->ln_feat.as<float>(), N, cls_feat, C, e->logits.as<float>(), st));
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
-            if (!tpt) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
-            if (kd) TRY(kd_teacher(e, n_sel, st));
+            if (kind != LOSS_TPT) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (loss_distils(kind)) TRY(kd_teacher(e, n_sel, st));
             TRY(launch_gather_rows(e->logits.as<float>(), C, e->sel_idx.as<int32_t>(), e->sel_logits.as<float>(), C, n_sel, C, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
             COPY_OUT(out->entropy, e->entropy.p, N * sizeof(float));
@@ -293,11 +238,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         } else {
             TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
         }
-        if (kd) TRY(kd_step(e, n_sel, a, st));
-        else if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));
-        else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
-                               a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
-                               e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
+        TRY(loss_step(e, a, kind, 1, n_sel, nullptr, nullptr, e->loss.as<float>(), st));
         if (j == 0) {
             RLCF_HIP_CHECK(hipMemsetAsync(e->bn_dlog.p, 0, (size_t)N * C * sizeof(float), st));
             TRY(launch_scatter_rows(e->dlogits.as<float>(), e->sel_idx.as<int32_t>(), e->bn_dlog.as<float>(), n_sel, C, st));
@@ -309,23 +250,11 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         TRY(rn_backward_bn(e, s, n, e->ln_feat.as<float>(), e->dfeat.as<float>(), e->ln_grad.as<float>(), st, full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            if (!kd && !tpt) {   // (the distillation and TPT losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
-                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
-            }
-            COPY_OUT(out->loss, e->loss.p, sizeof(float));
-            COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
+            TRY(loss_copy_out(e, out, kind, n_sel, n_e, st));
             COPY_OUT(out->ln_grad, e->ln_grad.p, nb);
         }
-        TRY(launch_grad_nonfinite(e->ln_grad.as<float>(), e->ln_count, 1, e->step_skip.as<int32_t>(), st));
-        if (full) TRY(launch_grad_nonfinite(e->vw_grad.as<float>(), (int64_t)e->vw_count, 1, e->step_skip.as<int32_t>(), st, true));
-        if (out->step_skipped) COPY_OUT(out->step_skipped + j, e->step_skip.p, sizeof(int32_t));
-        TRY(launch_adamw(e->ln_params.as<float>(), e->ln_grad.as<float>(), e->ln_m.as<float>(), e->ln_v.as<float>(), e->ln_count, j + 1,
-                         a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), e->ln_count));
+        TRY(visual_optim_step(e, a, j, full, out->step_skipped, st));
         if (full) {
-            TRY(launch_adamw(e->vw.as<float>(), e->vw_grad.as<float>(), e->vw_m.as<float>(), e->vw_v.as<float>(), (int64_t)e->vw_count, j + 1,
-                             a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), (int64_t)e->vw_count));
             e->vw_dirty = true;
             TRY(rn_visual_refresh(e, st));
         }
@@ -341,7 +270,7 @@ int engine_tta_sample_bn(rlcf_engine* e, const float* views, int N, const rlcf_t
         COPY_OUT(out->top5, e->top5.p, 5 * sizeof(int32_t));
     }
     RLCF_HIP_CHECK(hipMemcpyAsync(e->ln_params.p, e->ln_init.p, nb, hipMemcpyDeviceToDevice, st));
-    if (full) TRY(rn_visual_reset(e, st));
+    if (full) TRY(visual_reset(e, st));
     return RLCF_OK;
 }
 
@@ -355,26 +284,15 @@ int engine_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rl
     TRY(engine_visual_enable(e, st));
     return tta_sample_backbone(e, views, N, a, out, st, true);
 }
-static int visual_reset(rlcf_engine* e, hipStream_t st) {      // visual.load_state_dict(initial_state_dict) for the flat buffer
-    if (!e->vw_count || !e->vw_dirty) return RLCF_OK;
-    RLCF_HIP_CHECK(hipMemcpyAsync(e->vw.p, e->vw_init.p, e->vw_count * sizeof(float), hipMemcpyDeviceToDevice, st));
-    e->vw_dirty = false;
-    return engine_visual_refresh(e, st, e->vw_init_is_ckpt);
-}
 // rkd != NULL: retrieval distillation (rlcf_tta_retrieval_image_kd): rows in order, KD with these temperatures on every row
 static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st, bool full,
                                const rlcf_kd_params* rkd) {
     ClipModel& s = e->model[RLCF_STUDENT];
-    RLCF_ARG_CHECK(a);
-    TRY(tta_state_check(e, a));
-    RLCF_ARG_CHECK(N > 0 && N <= e->max_views && a->tta_steps >= 0 && sample_k_ok(e, a));
-    TRY(engine_tpt_check(a, full ? "rlcf_tta_sample_visual" : "rlcf_tta_sample_ln"));
-    const bool tpt = tpt_on(a);
+    RLCF_ARG_CHECK(a && N > 0 && N <= e->max_views && a->tta_steps >= 0);
+    const LossKind kind = loss_kind(a);
     const int C = e->C, K = a->sample_k, D = s.cfg.embed_dim;
     const int n_sel = n_selected(a, N), n_e = n_sel * K;
     if (a->tta_steps > 0 && n_sel <= 0) { rlcf_set_error("int(N*selection_p) == 0 views selected (N=%d, p=%g)", N, a->selection_p); return RLCF_ERR_ARG; }
-    TRY(kd_check(e, a, rkd != nullptr));
-    const bool kd = kd_mode(a) != 0;
     if (is_resnet(s.cfg)) {
         if (rkd) { rlcf_set_error("retrieval distillation tunes a ViT image encoder (CLIPRet_TTA)"); return RLCF_ERR_ARG; }
         return engine_tta_sample_bn(e, views, N, a, out, st, full);
@@ -405,42 +323,25 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             if (a->flags & RLCF_F_NO_SELECTION) TRY(launch_iota(e->sel_idx.as<int32_t>(), n_sel, st));     // retrieval: every row, in order
             TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
-            if (!tpt) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
-            if (kd) TRY(kd_teacher(e, n_sel, st));
+            if (kind != LOSS_TPT) TRY(reward_encode(e, n_sel, s.cfg.image_resolution, out->reward_image_features, st));
+            if (loss_distils(kind)) TRY(kd_teacher(e, n_sel, st));
             COPY_OUT(out->logits, e->logits.p, (size_t)N * C * sizeof(float));
             COPY_OUT(out->entropy, e->entropy.p, N * sizeof(float));
             COPY_OUT(out->selected_idx, e->sel_idx.p, n_sel * sizeof(int32_t));
         }
         TRY(vit_forward_saved(e, s, e->views_sel.as<float>(), n_sel, e->ln_feat.as<float>(), st));
         TRY(engine_logits(e, e->ln_feat.as<float>(), n_sel, cls_feat, C, e->sel_logits.as<float>(), st));
-        if (kd) TRY(kd_step(e, n_sel, a, st, rkd));
-        else if (tpt) TRY(tpt_step(e, 1, n_sel, e->loss.as<float>(), st));
-        else TRY(launch_reward_loss_bank(e->sel_logits.as<float>(), C, nullptr, 1, n_sel, C, K, reward_bank(e),
-                               a->clipscore_weight, a->flags, a->min_entropy_w, e->topk_idx.as<int32_t>(), e->clip_score.as<float>(),
-                               e->rewards.as<float>(), e->loss.as<float>(), e->dlogits.as<float>(), e->rl_stats.as<float>(), st));
+        TRY(loss_step(e, a, kind, 1, n_sel, rkd, nullptr, e->loss.as<float>(), st));
         if (full) RLCF_HIP_CHECK(hipMemsetAsync(e->vw_grad.p, 0, vb, st));
         TRY(vit_backward_ln(e, s, e->ln_feat.as<float>(), n_sel, e->dlogits.as<float>(), e->ln_grad.as<float>(), st, 1,
                             full ? e->vw_grad.as<float>() : nullptr));
         if (j == 0) {
             if (full) COPY_OUT(out->vis_grad, e->vw_grad.p, vb);
-            if (!kd && !tpt) {   // (the distillation and TPT losses sample no classes: topk_idx / clip_score / rewards stay unwritten)
-                COPY_OUT(out->topk_idx, e->topk_idx.p, (size_t)n_e * sizeof(int32_t));
-                COPY_OUT(out->clip_score, e->clip_score.p, (size_t)n_e * sizeof(float));
-                COPY_OUT(out->rewards, e->rewards.p, (size_t)n_e * sizeof(float));
-            }
-            COPY_OUT(out->loss, e->loss.p, sizeof(float));
-            COPY_OUT(out->dlogits, e->dlogits.p, (size_t)n_sel * C * sizeof(float));
+            TRY(loss_copy_out(e, out, kind, n_sel, n_e, st));
             COPY_OUT(out->ln_grad, e->ln_grad.p, nb);
         }
-        // one optimizer over both buffers: an inf / NaN anywhere skips the whole step (GradScaler.step, tpt_cls_rl.py:78)
-        TRY(launch_grad_nonfinite(e->ln_grad.as<float>(), e->ln_count, 1, e->step_skip.as<int32_t>(), st));
-        if (full) TRY(launch_grad_nonfinite(e->vw_grad.as<float>(), (int64_t)e->vw_count, 1, e->step_skip.as<int32_t>(), st, true));
-        if (out->step_skipped) COPY_OUT(out->step_skipped + j, e->step_skip.p, sizeof(int32_t));
-        TRY(launch_adamw(e->ln_params.as<float>(), e->ln_grad.as<float>(), e->ln_m.as<float>(), e->ln_v.as<float>(), e->ln_count, j + 1,
-                         a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), e->ln_count));
+        TRY(visual_optim_step(e, a, j, full, out->step_skipped, st));
         if (full) {
-            TRY(launch_adamw(e->vw.as<float>(), e->vw_grad.as<float>(), e->vw_m.as<float>(), e->vw_v.as<float>(), (int64_t)e->vw_count, j + 1,
-                             a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, st, e->step_skip.as<int32_t>(), (int64_t)e->vw_count));
             e->vw_dirty = true;
             TRY(engine_visual_refresh(e, st));
         }
@@ -462,28 +363,10 @@ static int tta_sample_backbone(rlcf_engine* e, const float* views, int N, const 
 }
 
 // ------------------------------------------------------------------ retrieval distillation (retrieval/clip_ret_kd.py)
-// what both retrieval KD entries refuse before anything is launched
-int engine_kd_refusals(const rlcf_engine* e, const rlcf_tta_args* a, const char* entry) {
-    if (a->flags & RLCF_F_MIN_ENTROPY) {
-        rlcf_set_error("%s: the distillation losses take no min-entropy regulariser (flags 0x%x)", entry, a->flags);
-        return RLCF_ERR_ARG;
-    }
-    if (a->flags & RLCF_F_DKD) {       // (RLCF_F_DKD is the high bit of the field: set in RLCF_F_DKD and RLCF_F_ATKD, clear in RLCF_F_KD)
-        rlcf_set_error("%s: retrieval distils with kd_distill_loss_v2 only (retrieval/clip_ret_kd.py has no DKD / ATKD form)", entry);
-        return RLCF_ERR_ARG;
-    }
-    if (e->n_rewards != 1) {
-        rlcf_set_error("the distillation losses need exactly one reward model (the engine holds %d)", e->n_rewards);
-        return RLCF_ERR_ARG;
-    }
-    return RLCF_OK;
-}
 // image -> text (clip_ret_kd.py:50-67): every-parameter tuning of the image encoder over all n query rows against the caption bank,
 // teacher = kd_teacher() once before the steps, loss = KD over the dense rows [n, C]
 int engine_tta_retrieval_image_kd(rlcf_engine* e, const float* images, int n, const rlcf_tta_args* a, const rlcf_kd_params* kd,
                                   const rlcf_tta_out* out, hipStream_t st) {
-    TRY(engine_kd_refusals(e, a, "rlcf_tta_retrieval_image_kd"));
-    if (e->C <= 0 || e->image_bank) { rlcf_set_error("class bank / reward model not set"); return RLCF_ERR_STATE; }
     const rlcf_kd_params p = kd ? *kd : kd_default_params();
     RLCF_ARG_CHECK(p.T_stu > 0.f && p.T_tea > 0.f);
     rlcf_tta_args b = *a;

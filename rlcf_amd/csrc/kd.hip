@@ -25,34 +25,6 @@
 
 #define KD_THREADS 256
 
-__device__ __forceinline__ double kd_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double kd_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double kd_block_sum(double v, double* red) {
-    v = kd_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < KD_THREADS / 64; ++i) s += red[i];
-    return s;
-}
-__device__ __forceinline__ double kd_block_max(double v, double* red) {
-    v = kd_wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < KD_THREADS / 64; ++i) s = fmax(s, red[i]);
-    return s;
-}
 // torch.argmax: first maximum, NaN ranks highest
 __device__ __forceinline__ bool kd_better(float a, int ia, float b, int ib) {
     if (a != a) return b == b || ia < ib;
@@ -82,10 +54,10 @@ __device__ int kd_block_argmax(const float* x, int C, float* redv, int* redi) {
 __device__ void kd_row_stats(const float* x, int C, double* red, double& mean, double& std) {
     double s = 0.0;
     for (int c = threadIdx.x; c < C; c += KD_THREADS) s += (double)x[c];
-    mean = kd_block_sum(s, red) / C;
+    mean = block_sum<KD_THREADS>(s, red) / C;
     double q = 0.0;
     for (int c = threadIdx.x; c < C; c += KD_THREADS) { const double d = (double)x[c] - mean; q += d * d; }
-    std = sqrt(kd_block_sum(q, red) / C);
+    std = sqrt(block_sum<KD_THREADS>(q, red) / C);
 }
 // p * (log p - lq) with torch.kl_div's convention 0 * log 0 = 0
 __device__ __forceinline__ double kd_kl_term(double p, double lp, double lq) { return p > 0.0 ? p * (lp - lq) : 0.0; }
@@ -137,17 +109,17 @@ __global__ __launch_bounds__(KD_THREADS) void kd_rows_kernel(const float* __rest
         mxs = fmax(mxs, zs); mxt = fmax(mxt, zt);
         if (c != g) { mxs_n = fmax(mxs_n, zs); mxt_n = fmax(mxt_n, zt); }
     }
-    mxs = kd_block_max(mxs, red); mxt = kd_block_max(mxt, red);
-    if (mode == RLCF_KD_DKD) { mxs_n = kd_block_max(mxs_n, red); mxt_n = kd_block_max(mxt_n, red); }
+    mxs = block_max<KD_THREADS>(mxs, red); mxt = block_max<KD_THREADS>(mxt, red);
+    if (mode == RLCF_KD_DKD) { mxs_n = block_max<KD_THREADS>(mxs_n, red); mxt_n = block_max<KD_THREADS>(mxt_n, red); }
     double ss = 0.0, st = 0.0, ss_n = 0.0, st_n = 0.0;
     for (int c = threadIdx.x; c < C; c += KD_THREADS) {
         const double zs = ((double)x[c] - as) * ks, zt = ((double)y[c] - at) * kt;
         ss += exp(zs - mxs); st += exp(zt - mxt);
         if (mode == RLCF_KD_DKD && c != g) { ss_n += exp(zs - mxs_n); st_n += exp(zt - mxt_n); }
     }
-    ss = kd_block_sum(ss, red); st = kd_block_sum(st, red);
+    ss = block_sum<KD_THREADS>(ss, red); st = block_sum<KD_THREADS>(st, red);
     const double lss = log(ss), lst = log(st);
-    if (mode == RLCF_KD_DKD) { ss_n = kd_block_sum(ss_n, red); st_n = kd_block_sum(st_n, red); }
+    if (mode == RLCF_KD_DKD) { ss_n = block_sum<KD_THREADS>(ss_n, red); st_n = block_sum<KD_THREADS>(st_n, red); }
     const double lss_n = log(ss_n), lst_n = log(st_n);
     if (mode != RLCF_KD_DKD) {
         // KD: -sum pt * log ps;  ATKD: sum pt * (log pt - log ps)
@@ -158,8 +130,8 @@ __global__ __launch_bounds__(KD_THREADS) void kd_rows_kernel(const float* __rest
             l += mode == RLCF_KD_KD ? -pt * lps : kd_kl_term(pt, lpt, lps);
             spt += pt;
         }
-        l = kd_block_sum(l, red) * out_scale;
-        spt = kd_block_sum(spt, red);
+        l = block_sum<KD_THREADS>(l, red) * out_scale;
+        spt = block_sum<KD_THREADS>(spt, red);
         if (threadIdx.x == 0) { row_acc[i] = l; if (row_loss) row_loss[i] = (float)l; }
         if (d) {
             const double gs = grad_scale * inv_n;
@@ -180,8 +152,8 @@ __global__ __launch_bounds__(KD_THREADS) void kd_rows_kernel(const float* __rest
         nckd += kd_kl_term(qt, lqt, lqs);
         sqt += qt;
     }
-    ps_o = kd_block_sum(ps_o, red); pt_o = kd_block_sum(pt_o, red);
-    nckd = kd_block_sum(nckd, red); sqt = kd_block_sum(sqt, red);
+    ps_o = block_sum<KD_THREADS>(ps_o, red); pt_o = block_sum<KD_THREADS>(pt_o, red);
+    nckd = block_sum<KD_THREADS>(nckd, red); sqt = block_sum<KD_THREADS>(sqt, red);
     const double zsg = ((double)x[g] - as) * ks, ztg = ((double)y[g] - at) * kt;
     const double lps_g = zsg - mxs - lss, lpt_g = ztg - mxt - lst, ps_g = exp(lps_g), pt_g = exp(lpt_g);
     // torch.log(pred_student) of the reference (float32): -inf when either merged probability is 0 there
@@ -284,14 +256,14 @@ __global__ __launch_bounds__(KD_THREADS) void kd_split_a_kernel(const float* __r
         zt[u] = in ? (double)y[c] * kt : -INFINITY;
         ms = fmax(ms, zs[u]); mt = fmax(mt, zt[u]);
     }
-    ms = kd_block_max(ms, red); mt = kd_block_max(mt, red);
+    ms = block_max<KD_THREADS>(ms, red); mt = block_max<KD_THREADS>(mt, red);
     double ss = 0.0, st = 0.0;
 #pragma unroll
     for (int u = 0; u < KD_SPLIT_PER; ++u) {
         const int c = c0 + u * KD_THREADS + threadIdx.x;
         if (c < C) { ss += exp(zs[u] - ms); st += exp(zt[u] - mt); }
     }
-    ss = kd_block_sum(ss, red); st = kd_block_sum(st, red);
+    ss = block_sum<KD_THREADS>(ss, red); st = block_sum<KD_THREADS>(st, red);
     if (threadIdx.x == 0) {
         double* w = ws + ((size_t)i * gridDim.x + k) * KD_SPLIT_WS;
         w[0] = ms; w[1] = ss; w[2] = mt; w[3] = st;
@@ -313,8 +285,8 @@ __global__ __launch_bounds__(KD_THREADS) void kd_split_b_kernel(const float* __r
     double cms = -INFINITY, css = 0.0, cmt = -INFINITY, cst = 0.0, wmt = 0.0;
     if (t < 64) {
         if (t < nch) { cms = wrow[t * KD_SPLIT_WS]; css = wrow[t * KD_SPLIT_WS + 1]; cmt = wrow[t * KD_SPLIT_WS + 2]; cst = wrow[t * KD_SPLIT_WS + 3]; }
-        const double wms = kd_wave_max(cms);
-        wmt = kd_wave_max(cmt);
+        const double wms = wave_max(cms);
+        wmt = wave_max(cmt);
         term_s[t] = t < nch ? css * exp(cms - wms) : 0.0;
         term_t[t] = t < nch ? cst * exp(cmt - wmt) : 0.0;
         if (t == 0) { stat[0] = wms; stat[1] = wmt; }
@@ -349,7 +321,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_split_b_kernel(const float* __r
             dot += (double)g * (double)xs;
         }
     }
-    l = kd_block_sum(l, red); dot = kd_block_sum(dot, red);
+    l = block_sum<KD_THREADS>(l, red); dot = block_sum<KD_THREADS>(dot, red);
     if (threadIdx.x == 0) { wrow[k * KD_SPLIT_WS + 4] = l; wrow[k * KD_SPLIT_WS + 5] = dot; }
 }
 

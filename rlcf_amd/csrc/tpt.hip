@@ -17,35 +17,6 @@
 #define TPT_THREADS 256
 #define TPT_MIN_REAL (-3.4028234663852886e38)      // torch.finfo(torch.float32).min
 
-__device__ __forceinline__ double tpt_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double tpt_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double tpt_block_sum(double v, double* red) {
-    v = tpt_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < TPT_THREADS / 64; ++i) s += red[i];
-    return s;
-}
-__device__ __forceinline__ double tpt_block_max(double v, double* red) {
-    v = tpt_wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < TPT_THREADS / 64; ++i) s = fmax(s, red[i]);
-    return s;
-}
-
 static int tpt_chunks(int C) { return (C + TPT_THREADS - 1) / TPT_THREADS; }
 size_t tpt_ws_bytes(int groups, int n, int C) {
     return ((size_t)groups * n + (size_t)groups * C + (size_t)groups * tpt_chunks(C)) * sizeof(double);
@@ -56,10 +27,10 @@ __global__ __launch_bounds__(TPT_THREADS) void tpt_rows_kernel(const float* __re
     const float* x = logits + (size_t)blockIdx.x * ld;
     double mx = -INFINITY;
     for (int c = threadIdx.x; c < C; c += TPT_THREADS) mx = fmax(mx, (double)x[c]);
-    mx = tpt_block_max(mx, red);
+    mx = block_max<TPT_THREADS>(mx, red);
     double s = 0.0;
     for (int c = threadIdx.x; c < C; c += TPT_THREADS) s += exp((double)x[c] - mx);       // (a NaN the max skipped lands here)
-    s = tpt_block_sum(s, red);
+    s = block_sum<TPT_THREADS>(s, red);
     if (threadIdx.x == 0) lse[blockIdx.x] = mx + log(s);
 }
 
@@ -81,7 +52,7 @@ __global__ __launch_bounds__(TPT_THREADS) void tpt_classes_kernel(const float* _
         a_out[(size_t)g * C + c] = a;
         h = a * exp(a);
     }
-    h = tpt_block_sum(h, red);
+    h = block_sum<TPT_THREADS>(h, red);
     if (threadIdx.x == 0) part[(size_t)g * gridDim.x + blockIdx.x] = h;
 }
 
@@ -102,7 +73,7 @@ __global__ __launch_bounds__(TPT_THREADS) void tpt_grad_kernel(const float* __re
     if (!dlogits) return;
     double dot = 0.0;
     for (int c = threadIdx.x; c < C; c += TPT_THREADS) dot += exp((double)x[c] - l) * a[c];
-    dot = tpt_block_sum(dot, red);
+    dot = block_sum<TPT_THREADS>(dot, red);
     const double inv_n = 1.0 / n;
     float* d = dlogits + (size_t)i * C;
     for (int c = threadIdx.x; c < C; c += TPT_THREADS) d[c] = (float)(exp((double)x[c] - l) * inv_n * (dot - a[c]));

@@ -7,24 +7,6 @@
 #define TTA_THREADS 256
 #define MAX_K 32                       // retrieval scripts sample 12 (text->image) and 20 (image->text) candidates
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int i = 0; i < TTA_THREADS / 64; ++i) s += red[i];
-    return s;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int i = 1; i < TTA_THREADS / 64; ++i) s = fmaxf(s, red[i]);
-    return s;
-}
 // Total order used by every selection here: NaN ranks ABOVE +inf (torch.topk / torch.argsort treat NaN as the largest value), so a
 // non-finite logits row still yields in-range, distinct indices (the GradScaler guard then skips the step: launch_grad_nonfinite).
 __device__ __forceinline__ bool ord_gt(float a, float b) { return a > b || (a != a && b == b); }
@@ -53,14 +35,14 @@ __global__ __launch_bounds__(TTA_THREADS) void row_entropy_kernel(const float* _
     const float* x = logits + (size_t)blockIdx.x * C;
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < C; c += TTA_THREADS) mx = fmaxf(mx, x[c]);
-    mx = block_max(mx, red);
+    mx = block_max<TTA_THREADS>(mx, red);
     float s = 0.f;
     for (int c = threadIdx.x; c < C; c += TTA_THREADS) s += expf(x[c] - mx);
-    s = block_sum(s, red);
+    s = block_sum<TTA_THREADS>(s, red);
     const float lse = mx + logf(s);
     float hsum = 0.f;
     for (int c = threadIdx.x; c < C; c += TTA_THREADS) { float lp = x[c] - lse; hsum += expf(lp) * lp; }
-    hsum = block_sum(hsum, red);
+    hsum = block_sum<TTA_THREADS>(hsum, red);
     if (threadIdx.x == 0) entropy[blockIdx.x] = -hsum;
 }
 // rank-select the n_sel lowest entropies, ascending (argsort semantics; ties by index)
@@ -132,10 +114,10 @@ __global__ __launch_bounds__(TTA_THREADS) void reward_stage_a_kernel(const float
     const float* x = logits + (size_t)(sel ? sel[i] : i) * ld;
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < C; c += TTA_THREADS) mx = fmaxf(mx, x[c]);
-    mx = block_max(mx, red);
+    mx = block_max<TTA_THREADS>(mx, red);
     float s = 0.f;
     for (int c = threadIdx.x; c < C; c += TTA_THREADS) s += expf(x[c] - mx);
-    s = block_sum(s, red);
+    s = block_sum<TTA_THREADS>(s, red);
     const float lse = mx + logf(s);
     for (int k = 0; k < K; ++k) {                      // torch.topk order: descending value
         float bv = -INFINITY; int bi = 0x7fffffff;
@@ -161,7 +143,7 @@ __global__ __launch_bounds__(TTA_THREADS) void reward_stage_a_kernel(const float
             const float* im = bank.reward_img[m] + (size_t)i * Dr;
             float d = 0.f;
             for (int c = threadIdx.x; c < Dr; c += TTA_THREADS) d += t[c] * im[c];
-            d = block_sum(d, red);
+            d = block_sum<TTA_THREADS>(d, red);
             score += bank.mix[m] * relu_nan(weight * d);
         }
         if (threadIdx.x == 0) stats[i * STAT_LD + 1 + MAX_K + k] = bank.post_div == 1.f ? score : score / bank.post_div;
@@ -250,8 +232,8 @@ __global__ __launch_bounds__(TTA_THREADS) void reward_stage_b_kernel(const float
             pa_dot += expf(x[c] - lse) * a;
             hreg += a * expf(a);
         }
-        pa_dot = block_sum(pa_dot, red);
-        hreg = block_sum(hreg, red);
+        pa_dot = block_sum<TTA_THREADS>(pa_dot, red);
+        hreg = block_sum<TTA_THREADS>(hreg, red);
     }
     __syncthreads();
     if (first && threadIdx.x == 0 && loss) loss[0] = r_all_sum + (minent ? -min_entropy_w * hreg : 0.f);
@@ -472,10 +454,10 @@ __global__ __launch_bounds__(TTA_THREADS) void avg_entropy_kernel(const float* _
         const float* row = x + (size_t)r * C;
         float m = -INFINITY;
         for (int c = threadIdx.x; c < C; c += TTA_THREADS) { const float v = row[c]; bad += (v != v || v == INFINITY) ? 1.f : 0.f; m = fmaxf(m, v); }
-        m = block_max(m, red);
+        m = block_max<TTA_THREADS>(m, red);
         float sum = 0.f;
         for (int c = threadIdx.x; c < C; c += TTA_THREADS) sum += expf(row[c] - m);
-        sum = block_sum(sum, red);
+        sum = block_sum<TTA_THREADS>(sum, red);
         if (threadIdx.x == 0) lse[r] = m + logf(sum);
         __syncthreads();
     }
@@ -490,8 +472,8 @@ __global__ __launch_bounds__(TTA_THREADS) void avg_entropy_kernel(const float* _
         a = fmaxf(a, -3.402823466e+38f);          // (torch.clamp(min = finfo(float32).min))
         acc -= a * expf(a);
     }
-    acc = block_sum(acc, red);
-    bad = block_sum(bad, red);
+    acc = block_sum<TTA_THREADS>(acc, red);
+    bad = block_sum<TTA_THREADS>(bad, red);
     if (threadIdx.x == 0) out[0] = bad > 0.f ? NAN : acc;
 }
 int launch_avg_entropy(const float* logits, int n, int C, float* out, hipStream_t st) {

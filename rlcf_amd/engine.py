@@ -259,31 +259,20 @@ class Engine:
     def tta_sample(self, views: torch.Tensor, cfg: TTAConfig, want_intermediates: bool = True, skip_final: bool = False,
                    ctx_in: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         views = views.to(self.device, torch.float32).contiguous()
-        N, Cn, K = views.shape[0], self.n_cls, cfg.sample_k
-        n_sel = cfg.n_sel(N)
-        Wt = self.student.transformer_width
-        Dr = sum(r.embed_dim for r in self.rewards)     # per-model blocks [n_sel, Dr_m], one after another
+        N, n_sel = views.shape[0], cfg.n_sel(views.shape[0])
         dev = self.device
-        o: Dict[str, torch.Tensor] = {
-            "final_logits": torch.empty(1, Cn, device=dev), "top5": torch.empty(5, dtype=torch.int32, device=dev),
-            "ctx_after": torch.empty(self.n_ctx, Wt, device=dev),
-            "step_skipped": torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev)}
+        fields = ["final_logits", "top5", "ctx_after", "step_skipped"]
         if want_intermediates and cfg.tta_steps > 0:
-            o.update(logits=torch.empty(N, Cn, device=dev), entropy=torch.empty(N, device=dev),
-                     selected_idx=torch.empty(n_sel, dtype=torch.int32, device=dev),
-                     topk_idx=torch.empty(n_sel, K, dtype=torch.int32, device=dev),
-                     clip_score=torch.empty(n_sel * K, device=dev), rewards=torch.empty(n_sel * K, device=dev),
-                     loss=torch.empty(1, device=dev), dlogits=torch.empty(n_sel, Cn, device=dev),
-                     ctx_grad=torch.empty(self.n_ctx, Wt, device=dev),
-                     reward_image_features=torch.empty(n_sel * Dr, device=dev))
-            self._kd_outputs(o, cfg, n_sel)
+            fields += ["logits", "entropy", "selected_idx", "topk_idx", "clip_score", "rewards", "loss", "dlogits", "ctx_grad", "reward_image_features"]
+        # reward features: per-model blocks [n_sel, Dr_m], one after another
+        o = self._outputs(fields, cfg, N, n_sel, reward_dim=sum(r.embed_dim for r in self.rewards))
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         if ctx_in is not None:
             ctx_in = ctx_in.detach().to(dev, torch.float32).contiguous()
         a = cfg.c_args(N, skip_final, ctx_in)
         L.check(self.lib.rlcf_tta_sample(self.h, _ptr(views), N, C.byref(a), C.byref(co), _stream()), "tta_sample")
         if "reward_image_features" in o:
-            parts = torch.split(o["reward_image_features"], [n_sel * r.embed_dim for r in self.rewards])
+            parts = torch.split(o["reward_image_features"].view(-1), [n_sel * r.embed_dim for r in self.rewards])
             parts = [p.view(n_sel, r.embed_dim) for p, r in zip(parts, self.rewards)]
             o["reward_image_features"] = parts[0] if len(parts) == 1 else parts
         return o
@@ -317,38 +306,47 @@ class Engine:
         L.check(self.lib.rlcf_engine_reset_visual_state(self.h, _stream()), "reset_visual_state")
         self.reset_moved = False
 
-    def _kd_outputs(self, o: Dict[str, torch.Tensor], cfg: TTAConfig, n_sel: int) -> None:
-        """a distillation-loss call samples no classes (topk_idx / clip_score / rewards stay unwritten, so they are not returned);
-        it returns the first step's dlogits and the reward features of the selected views, the teacher's input"""
-        if not cfg.kd_loss and not cfg.tpt:
-            return
-        for k in ("topk_idx", "clip_score", "rewards"):
-            o.pop(k, None)
-        o["dlogits"] = torch.empty(n_sel, self.n_cls, device=self.device)
-        if cfg.tpt:                    # (no reward pass under RLCF_F_TPT: reward_image_features stays unwritten too)
-            o.pop("reward_image_features", None)
-        else:
-            o["reward_image_features"] = torch.empty(n_sel, self.reward.embed_dim, device=self.device)
+    _INT_OUTPUTS = ("top5", "selected_idx", "topk_idx", "step_skipped")
+
+    def _outputs(self, fields, cfg: TTAConfig, N: int, n_sel: int, n_ln: int = 0, n_flat: int = 0, distil: bool = False,
+                 reward_dim: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """The output tensors of a tuning call: `fields` as the reward loss fills them, for N rows of which n_sel carry the loss, n_ln /
+        n_flat floats in the norm-layer / flat parameter vectors.  A distillation call (cfg.kd_loss, or distil: the retrieval *_kd
+        entries) and a TPT call (cfg.tpt) sample no classes: topk_idx / clip_score / rewards stay unwritten, so they are not returned;
+        they return the first step's dlogits, and the distillation call the reward features of its rows, the teacher's input (no
+        reward pass under RLCF_F_TPT: reward_image_features stays unwritten too).  reward_dim: reward features per row (default: the
+        first reward model's)."""
+        fields = list(fields)
+        if (distil or cfg.kd_loss or cfg.tpt) and "loss" in fields:
+            fields = [f for f in fields if f not in ("topk_idx", "clip_score", "rewards", "dlogits", "reward_image_features")] + ["dlogits"]
+            if not cfg.tpt:
+                fields.append("reward_image_features")
+        Cn, K, Wt = self.n_cls, cfg.sample_k, self.student.transformer_width
+        shape = {"final_logits": (1, Cn), "top5": (5,), "step_skipped": (max(cfg.tta_steps, 1),), "logits": (N, Cn), "entropy": (N,),
+                 "selected_idx": (n_sel,), "topk_idx": (n_sel, K), "clip_score": (n_sel * K,), "rewards": (n_sel * K,), "loss": (1,),
+                 "dlogits": (n_sel, Cn), "ctx_after": (self.n_ctx, Wt), "ctx_grad": (self.n_ctx, Wt), "ln_after": (n_ln,), "ln_grad": (n_ln,),
+                 "vis_after": (n_flat,), "vis_grad": (n_flat,)}
+        if "reward_image_features" in fields:
+            shape["reward_image_features"] = (n_sel, self.reward.embed_dim if reward_dim is None else reward_dim)
+        o = {f: torch.empty(shape[f], dtype=torch.int32 if f in self._INT_OUTPUTS else torch.float32, device=self.device) for f in fields}
+        o["step_skipped"].zero_()
+        return o
 
     def kd_loss(self, student: torch.Tensor, teacher: torch.Tensor, kind: str = "KD", target: Optional[torch.Tensor] = None,
                 params: Optional[L.KdParams] = None, row_loss: bool = False):
         """rlcf_kd_loss: (loss [1], dlogits [n, C], row losses [n] or None) of one distillation loss (include/rlcf_hip.h)"""
         return kd_loss_op(student, teacher, KD_MODES[kind], target, params, row_loss)
 
+    _NORM_FIELDS = ("final_logits", "top5", "ln_after", "ln_grad", "step_skipped", "logits", "selected_idx", "topk_idx", "clip_score", "rewards", "loss")
+    _VISUAL_FIELDS = _NORM_FIELDS + ("vis_after", "vis_grad")
+    _TEXT_FIELDS = ("final_logits", "logits", "dlogits", "ln_after", "ln_grad", "vis_after", "vis_grad", "step_skipped", "reward_image_features",
+                    "topk_idx", "clip_score", "rewards", "loss")
+
     def tta_sample_ln(self, views: torch.Tensor, cfg: TTAConfig, skip_final: bool = False) -> Dict[str, torch.Tensor]:
         """LayerNorm-tuning step (reference TPT/tune_cls_rl.py with CLIPCLS_TTA(only_norm=True))."""
         views = views.to(self.device, torch.float32).contiguous()
-        N, Cn, K = views.shape[0], self.n_cls, cfg.sample_k
-        n_sel = cfg.n_sel(N)
-        npar = int(self.lib.rlcf_engine_ln_param_count(self.h))
-        dev = self.device
-        o = dict(final_logits=torch.empty(1, Cn, device=dev), top5=torch.empty(5, dtype=torch.int32, device=dev),
-                 ln_after=torch.empty(npar, device=dev), ln_grad=torch.empty(npar, device=dev),
-                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
-                 logits=torch.empty(N, Cn, device=dev), selected_idx=torch.empty(n_sel, dtype=torch.int32, device=dev),
-                 topk_idx=torch.empty(n_sel, K, dtype=torch.int32, device=dev), clip_score=torch.empty(n_sel * K, device=dev),
-                 rewards=torch.empty(n_sel * K, device=dev), loss=torch.empty(1, device=dev))
-        self._kd_outputs(o, cfg, n_sel)
+        N, n_sel = views.shape[0], cfg.n_sel(views.shape[0])
+        o = self._outputs(self._NORM_FIELDS, cfg, N, n_sel, n_ln=int(self.lib.rlcf_engine_ln_param_count(self.h)))
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(N, skip_final)
         L.check(self.lib.rlcf_tta_sample_ln(self.h, _ptr(views), N, C.byref(a), C.byref(co), _stream()), "tta_sample_ln")
@@ -486,21 +484,12 @@ class Engine:
     def tta_sample_visual(self, views: torch.Tensor, cfg: TTAConfig, skip_final: bool = False, retrieval: bool = False) -> Dict[str, torch.Tensor]:
         """Full image-encoder tuning step (reference TPT/tune_cls_rl.py with CLIPCLS_TTA(only_norm=False), scripts/rlcf-tune.sh)."""
         views = views.to(self.device, torch.float32).contiguous()
-        N, Cn, K = views.shape[0], self.n_cls, cfg.sample_k
-        n_sel = N if retrieval else cfg.n_sel(N)
+        N = views.shape[0]
         npar = int(self.lib.rlcf_engine_ln_param_count(self.h))
         nvis = int(self.lib.rlcf_engine_visual_param_count(self.h, _stream()))
         if nvis <= 0:
             L.check(-1, "tta_sample_visual (visual_param_count)")
-        dev = self.device
-        o = dict(final_logits=torch.empty(1, Cn, device=dev), top5=torch.empty(5, dtype=torch.int32, device=dev),
-                 ln_after=torch.empty(npar, device=dev), ln_grad=torch.empty(npar, device=dev),
-                 vis_after=torch.empty(nvis, device=dev), vis_grad=torch.empty(nvis, device=dev),
-                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
-                 logits=torch.empty(N, Cn, device=dev), selected_idx=torch.empty(n_sel, dtype=torch.int32, device=dev),
-                 topk_idx=torch.empty(n_sel, K, dtype=torch.int32, device=dev), clip_score=torch.empty(n_sel * K, device=dev),
-                 rewards=torch.empty(n_sel * K, device=dev), loss=torch.empty(1, device=dev))
-        self._kd_outputs(o, cfg, n_sel)
+        o = self._outputs(self._VISUAL_FIELDS, cfg, N, N if retrieval else cfg.n_sel(N), n_ln=npar, n_flat=nvis)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(N, skip_final)
         fn = self.lib.rlcf_tta_retrieval_image if retrieval else self.lib.rlcf_tta_sample_visual
@@ -518,18 +507,12 @@ class Engine:
         """Image -> text retrieval distillation step: tune_image of retrieval/clip_ret_kd.py:50-67 (+ the evaluation of its loop) over
         the caption bank given to set_class_bank(n_ctx=0).  cfg supplies tta_steps and the AdamW hyper-parameters only."""
         images = images.to(self.device, torch.float32).contiguous()
-        N, Cn = images.shape[0], self.n_cls
+        N = images.shape[0]
         npar = int(self.lib.rlcf_engine_ln_param_count(self.h))
         nvis = int(self.lib.rlcf_engine_visual_param_count(self.h, _stream()))
         if nvis <= 0:
             L.check(-1, "tta_retrieval_image_kd (visual_param_count)")
-        dev = self.device
-        o = dict(final_logits=torch.empty(1, Cn, device=dev), top5=torch.empty(5, dtype=torch.int32, device=dev),
-                 ln_after=torch.empty(npar, device=dev), ln_grad=torch.empty(npar, device=dev),
-                 vis_after=torch.empty(nvis, device=dev), vis_grad=torch.empty(nvis, device=dev),
-                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
-                 logits=torch.empty(N, Cn, device=dev), dlogits=torch.empty(N, Cn, device=dev), loss=torch.empty(1, device=dev),
-                 reward_image_features=torch.empty(N, self.reward.embed_dim, device=dev))
+        o = self._outputs([f for f in self._VISUAL_FIELDS if f != "selected_idx"], cfg, N, N, n_ln=npar, n_flat=nvis, distil=True)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(N, skip_final)
         a.flags &= ~(L.F_REWARD_PROCESS | L.F_AMPLIFY | L.F_PROCESS_BATCH)
@@ -550,12 +533,7 @@ class Engine:
         nflat = int(self.lib.rlcf_engine_text_param_count(self.h, C.byref(ln_count), _stream()))
         if nflat <= 0:
             L.check(-1, "tta_retrieval_text_kd (text_param_count)")
-        dev, n = self.device, self.n_cls
-        o = dict(final_logits=torch.empty(1, n, device=dev), logits=torch.empty(1, n, device=dev), dlogits=torch.empty(1, n, device=dev),
-                 ln_after=torch.empty(ln_count.value, device=dev), ln_grad=torch.empty(ln_count.value, device=dev),
-                 vis_after=torch.empty(nflat, device=dev), vis_grad=torch.empty(nflat, device=dev),
-                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
-                 reward_image_features=torch.empty(1, self.rewards[0].embed_dim, device=dev), loss=torch.empty(1, device=dev))
+        o = self._outputs(self._TEXT_FIELDS, cfg, 1, 1, n_ln=ln_count.value, n_flat=nflat, distil=True)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(1, skip_final)
         a.flags &= ~(L.F_REWARD_PROCESS | L.F_AMPLIFY | L.F_PROCESS_BATCH)
@@ -632,15 +610,7 @@ class Engine:
         nflat = int(self.lib.rlcf_engine_text_param_count(self.h, C.byref(ln_count), _stream()))
         if nflat <= 0:
             L.check(-1, "tta_retrieval_text (text_param_count)")
-        dev, n, K = self.device, self.n_cls, cfg.sample_k
-        Dr = self.rewards[0].embed_dim
-        o = dict(final_logits=torch.empty(1, n, device=dev), logits=torch.empty(1, n, device=dev), dlogits=torch.empty(1, n, device=dev),
-                 ln_after=torch.empty(ln_count.value, device=dev), ln_grad=torch.empty(ln_count.value, device=dev),
-                 vis_after=torch.empty(nflat, device=dev), vis_grad=torch.empty(nflat, device=dev),
-                 step_skipped=torch.zeros(max(cfg.tta_steps, 1), dtype=torch.int32, device=dev),
-                 reward_image_features=torch.empty(1, Dr, device=dev),
-                 topk_idx=torch.empty(1, K, dtype=torch.int32, device=dev), clip_score=torch.empty(K, device=dev),
-                 rewards=torch.empty(K, device=dev), loss=torch.empty(1, device=dev))
+        o = self._outputs(self._TEXT_FIELDS, cfg, 1, 1, n_ln=ln_count.value, n_flat=nflat)
         co = L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
         a = cfg.c_args(1, skip_final)
         L.check(self.lib.rlcf_tta_retrieval_text(self.h, tok.data_ptr(), C.byref(a), C.byref(co), _stream()), "tta_retrieval_text")
