@@ -97,6 +97,11 @@ int rlcf_split_f16x2(const float* x, void* hi, void* lo, int64_t n, rlcf_stream 
 int rlcf_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi, const void* Wlo, int ldw, const float* bias,
                     const float* residual, int ldr, const float* aux, int ldaux, float* C, int ldc, void* Chi, void* Clo,
                     int ldch, int M, int N, int K, float alpha, int epilogue, rlcf_stream stream);
+/* The same call for a weight the caller KNOWS to sit on the f16 grid (every lo half of W is zero: a released checkpoint's weights):
+ * the product a_hi . w_lo adds exact zeros and is dropped — two MFMA passes, the same bits.  What the engine does per weight at finalize. */
+int rlcf_gemm_f16x3_grid_w(const void* Ahi, const void* Alo, int lda, const void* Whi, const void* Wlo, int ldw, const float* bias,
+                           const float* residual, int ldr, const float* aux, int ldaux, float* C, int ldc, void* Chi, void* Clo,
+                           int ldch, int M, int N, int K, float alpha, int epilogue, rlcf_stream stream);
 
 /* Single-pass f16 GEMM (RLCF_PREC_F16, the labelled performance mode — NOT parity-grade): the arithmetic of the reference's own GPU runs,
  * every nn.Linear of TPT/clip/model.py:171-192 under torch.cuda.amp.autocast() (TPT/tpt_cls_rl.py:52,182,261): f16 operands, one f16 MFMA

@@ -3,8 +3,18 @@
 // Every f32 operand x is carried as two f16 numbers  x = hi + lo,  hi = f16(x),  lo = f16(x - hi)
 // (22 significant bits while lo is a normal f16, i.e. |x| >= 2^-3; below that the ABSOLUTE error is <= 2^-25 — weights
 // are therefore pre-multiplied by an exact power of two at split time, undone in alpha), and a product a*b is evaluated
-// as  ahi*bhi + ahi*blo + alo*bhi  with THREE v_mfma_f32_32x32x16_f16 into ONE f32 accumulator (each f16 x f16 product is
-// exact in f32); the dropped lo*lo term is 2^-22 relative.  Measured on the ViT-B/16 image tower the
+// as  ahi*bhi + ahi*blo + alo*bhi  with THREE MFMAs into ONE f32 accumulator (each f16 x f16 product is
+// exact in f32); the dropped lo*lo term is 2^-22 relative.
+//
+// INVARIANT of the kernel family (gemm_nt_f16x3_kernel, _v2, _v3, _v3i; X3_MFMA16 = 1, the default build):
+//   Per output element and per 32-wide K block, ONE v_mfma_f32_16x16x32_f16 per product (k = 32), in the order hi.hi, hi.lo, lo.hi,
+//   K blocks in increasing order.
+// (SINGLE: hi.hi, lo.lo; WLO0: the middle product dropped.)  Whichever kernel the launcher picks for a product therefore gives the
+// same bits.  `make X3_MFMA16=0` builds the family on v_mfma_f32_32x32x16_f16 instead (two k-substeps of 16 per K block, the three
+// products per substep): the two shapes sum inside the instruction in different orders, so the family moves as a whole and the
+// shape is a compile-time constant (gemm_x3.h), never a run-time choice.  gemm_skinny_x3_kernel (launch-bound, its own operand
+// scaling) and the experimental gemm_nt_f16x3_v4_kernel stay on 32x32x16 in both builds.
+// Fragment map of 16x16x32: lane l holds row (column) l & 15, k = 8 (l >> 4) + j of the K block; C/D: column l & 15, row 4 (l >> 4) + reg.  Measured on the ViT-B/16 image tower the
 // feature error vs f64 is 6.9e-8 (plain f32: 6.1e-8, plain f16: 5.3e-5, bf16: 4.7e-4), i.e. the
 // 1e-3 logit tolerance of the RLCF parity contract holds with the margin of the f32 path while
 // the contraction runs on the 2.5 PF f16 MFMA pipe instead of the 157 TF f32 one.
@@ -25,6 +35,25 @@
 #define X3_LD 40                        // halves per LDS row (32 + 8 pad = 80 B)
 #define X3_TILE (X3_BM * X3_LD)         // halves per operand tile
 
+#if X3_MFMA16
+__device__ __forceinline__ f32x4 x3_mfma16(h16x8 a, h16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+// One 16-row tile (fragments AH / AL) against the 16-column tiles [c0, c0 + NC) of the wave (BH[] / BL[]), into ACC[] (f32x4 per column
+// tile), PASS BY PASS: no MFMA directly follows its predecessor on the same accumulator, and each accumulator takes hi.hi, hi.lo,
+// lo.hi in that order.  SINGLE / WLO0: constexpr in scope (WLO0: the weight's lo halves are all zero, hi.lo dropped)
+#define X3_MMA16(ACC, c0, NC, AH, AL, BH, BL)                                                                            \
+    {                                                                                                                    \
+        _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (NC); ++j_) ACC[j_] = x3_mfma16(AH, BH[j_], ACC[j_]);          \
+        if constexpr (SINGLE) {                                                                                          \
+            _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (NC); ++j_) ACC[j_] = x3_mfma16(AL, BL[j_], ACC[j_]);      \
+        } else {                                                                                                         \
+            if constexpr (!WLO0) {                                                                                       \
+                _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (NC); ++j_) ACC[j_] = x3_mfma16(AH, BL[j_], ACC[j_]);  \
+            }                                                                                                            \
+            _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (NC); ++j_) ACC[j_] = x3_mfma16(AL, BH[j_], ACC[j_]);      \
+        }                                                                                                                \
+    }
+#endif
+
 template <bool SINGLE>
 __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
     float am = 0.f;                 // max|C| of this thread's outputs (amax_out)
@@ -43,6 +72,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, h = lane >> 5;
 
+#if X3_MFMA16
+    constexpr bool WLO0 = false;
+    const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 8-wide k group of this lane
+    (void)l32; (void)h;
+    f32x4 acc[4][4];                                // 16-row tiles x 16-column tiles of the wave's 64 x 64
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#else
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -50,6 +89,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#endif
 
     // staging: each operand tile = 128 rows x 64 B = 512 16-B chunks, 2 per thread (rows r0 and r0+64)
     const int r0 = t >> 2, c8 = (t & 3) * 8;
@@ -77,12 +117,32 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
     X3_GLOAD(0)
     X3_LSTORE(0)
     __syncthreads();
+#if X3_MFMA16
+    // (80-byte rows: the 16 rows of a 16-lane ds_read_b128 group start 5 r mod 16 sixteen-byte slots apart — all distinct)
+    const int arow = (wm * 64 + l16) * X3_LD + kq * 8;
+    const int brow = (wn * 64 + l16) * X3_LD + kq * 8;
+#else
     const int arow = (wm * 64 + l32) * X3_LD + h * 8;
     const int brow = (wn * 64 + l32) * X3_LD + h * 8;
+#endif
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) { X3_GLOAD((kt + 1) * g.kstep) }
         const _Float16* base = lds + cur * 4 * X3_TILE;
+#if X3_MFMA16
+        {
+            h16x8 ah[4], al[4], bh[4], bl[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ah[i] = *(const h16x8*)(base + 0 * X3_TILE + arow + i * 16 * X3_LD);
+                al[i] = *(const h16x8*)(base + 1 * X3_TILE + arow + i * 16 * X3_LD);
+                bh[i] = *(const h16x8*)(base + 2 * X3_TILE + brow + i * 16 * X3_LD);
+                bl[i] = *(const h16x8*)(base + 3 * X3_TILE + brow + i * 16 * X3_LD);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) X3_MMA16(acc[i], 0, 4, ah[i], al[i], bh, bl)
+        }
+#else
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             h16x8 ah[2], al[2], bh[2], bl[2];
@@ -106,6 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
                     }
                 }
         }
+#endif
         if (kt + 1 < nk) X3_LSTORE(cur ^ 1)
         __syncthreads();
     }
@@ -114,6 +175,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
         // epilogue through LDS (see v2): 16-byte row-wise accesses instead of 64 scalar ones per lane
         constexpr int ELD = 68;
         float* park = (float*)lds + wave * (64 * ELD);
+#if X3_MFMA16
+        x3_park16<4>(park, &acc[0][0], lane);
+#else
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -121,6 +185,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[i][j][r];
+#endif
         __syncthreads();
         const int c4 = (lane & 15) * 4, rsub = lane >> 4;
         const int col = n0 + wn * 64 + c4;
@@ -165,16 +230,29 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
+#if X3_MFMA16
+    constexpr int NTI = 4, NTJ = 4, NR = 4;
+#else
+    constexpr int NTI = 2, NTJ = 2, NR = 16;
+#endif
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < NTI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < NTJ; ++j) {
+#if X3_MFMA16
+            const int col = n0 + wn * 64 + j * 16 + l16;
+#else
             const int col = n0 + wn * 64 + j * 32 + l32;
+#endif
             if (col >= g.N) continue;
             const float bv = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
+            for (int r = 0; r < NR; ++r) {
+#if X3_MFMA16
+                const int row = m0 + wm * 64 + i * 16 + 4 * kq + r;
+#else
                 const int row = m0 + wm * 64 + i * 32 + mfma32_row(r, h);
+#endif
                 if (row >= g.M) continue;
                 float v = x3_alpha(g) * acc[i][j][r] + bv;
                 if (g.epilogue == RLCF_EPI_QUICKGELU) v = quick_gelu_fast(v);
@@ -235,6 +313,15 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, h = lane >> 5;
 
+#if X3_MFMA16
+    const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 16-byte k chunk of this lane
+    (void)l32; (void)h; (void)kq;
+    f32x4 acc[2 * RT][4];                           // 16-row tiles x 16-column tiles of the wave's (32 RT) x 64
+#pragma unroll
+    for (int i = 0; i < 2 * RT; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#else
     f32x16 acc[RT][2];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
@@ -242,6 +329,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#endif
 
     // DMA sources: A tile = BM x 4 chunks (RT wave-instructions per wave per array), W tile = 512 (WPW each)
     const int qa0 = (wave * RT) * 64 + lane, qa1 = qa0 + 64, qw = (wave * WPW) * 64 + lane, qw1 = qw + 64;
@@ -311,6 +399,20 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BH[1], acc[i][1], 0, 0, 0);                            \
     }
 #define V2_FENCE __builtin_amdgcn_sched_barrier(0);
+// 16x16x32 fragments of the 64-byte-row image: lane l reads chunk l >> 4 (k = 8 (l >> 4) ..) of row base + (l & 15), slot chunk ^ ((r >> 2) & 3).
+// Bank map of a 16-lane ds_read_b128 group (16 consecutive rows, one chunk): row r starts at bank 16 (r & 3), its slot adds
+// 4 (chunk ^ (r >> 2)): the four rows of a class r & 3 take the four slots, the 16 lanes cover all 64 banks — the case the swizzle was
+// built for, unchanged.  Row tiles [t0, t0 + n) of A, column tiles [c0, c0 + n) of W
+#define V2_LDA16(t0, n, AH, AL)                                                                                          \
+    _Pragma("unroll") for (int i_ = (t0); i_ < (t0) + (n); ++i_) {                                                       \
+        AH[i_] = *(const h16x8*)(sb + aoff + i_ * 1024 + co16);                                                          \
+        AL[i_] = *(const h16x8*)(sb + ALO + aoff + i_ * 1024 + co16);                                                    \
+    }
+#define V2_LDB16(c0, n, BH, BL)                                                                                          \
+    _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (n); ++j_) {                                                       \
+        BH[j_] = *(const h16x8*)(sb + WHI + boff + j_ * 1024 + co16);                                                    \
+        BL[j_] = *(const h16x8*)(sb + WLO + boff + j_ * 1024 + co16);                                                    \
+    }
 
     // split-K (a few tiles, long K loop): this block walks K tiles [kt0, kt0 + nk) and leaves its raw partial tile in g.ws
     int nk = g.K / X3_BK, kt0 = 0;
@@ -322,8 +424,13 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     const int kb = kt0 * g.kstep;
     V2_ISSUE(kb, 0)
     if (nk > 1) V2_ISSUE(kb + g.kstep, 1)
+#if X3_MFMA16
+    const int aoff = (wm * (32 * RT) + l16) * 64, boff = (wn * 64 + l16) * 64;      // row byte offsets
+    const int co16 = (kq ^ ((l16 >> 2) & 3)) * 16;
+#else
     const int swz = (l32 >> 2) & 3;
     const int aoff = (wm * (32 * RT) + l32) * 64, boff = (wn * 64 + l32) * 64;      // row byte offsets
+#endif
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");      // the NP pieces of the newest stage may stay in flight
@@ -334,6 +441,45 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         const int kn = kb + (kt + 2) * g.kstep;
         char* sn = smem + (cur >= 1 ? cur - 1 : 2) * STAGE;                // stage (cur + 2) % 3
         const char* sb = smem + cur * STAGE;
+#if X3_MFMA16
+        // 2 RT row tiles x two halves (column tiles 0-1 / 2-3) = the same number of MFMA groups of the same length as the 32x32x16 form
+        // (6 MFMAs of k = 32 for 3 of twice the size), the DMA pieces between the same groups.  Only what the first group needs (6 fragments)
+        // is read before it: nothing hides the LDS latency after the barrier on the small grids these forms serve
+        h16x8 ah[2 * RT], al[2 * RT], bh[4], bl[4];
+        V2_LDA16(0, 1, ah, al) V2_LDB16(0, 2, bh, bl)
+        V2_FENCE
+        X3_MMA16(acc[0], 0, 2, ah[0], al[0], bh, bl) V2_FENCE
+        if (pf) V2_PIECE(0, kn, sn)
+        V2_LDB16(2, 2, bh, bl) V2_LDA16(1, 2 * RT - 1, ah, al)
+        V2_FENCE
+        X3_MMA16(acc[0], 2, 2, ah[0], al[0], bh, bl) V2_FENCE
+        if constexpr (RT == 2) {
+            if (pf) V2_PIECE(1, kn, sn)
+            V2_FENCE
+            X3_MMA16(acc[1], 0, 2, ah[1], al[1], bh, bl) V2_FENCE
+            if (pf) V2_PIECE(2, kn, sn)
+            V2_FENCE
+            X3_MMA16(acc[1], 2, 2, ah[1], al[1], bh, bl) V2_FENCE
+            if (pf) V2_PIECE(3, kn, sn)
+            V2_FENCE
+            X3_MMA16(acc[2], 0, 2, ah[2], al[2], bh, bl) V2_FENCE
+            if (pf) { V2_PIECE(4, kn, sn) V2_PIECE(6, kn, sn) }
+            V2_FENCE
+            X3_MMA16(acc[2], 2, 2, ah[2], al[2], bh, bl) V2_FENCE
+            if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
+            V2_FENCE
+            X3_MMA16(acc[3], 0, 2, ah[3], al[3], bh, bl)
+            X3_MMA16(acc[3], 2, 2, ah[3], al[3], bh, bl)
+        } else {                            // two 16-row tiles per wave: four MFMA groups, the four pieces (A hi, A lo, W hi, W lo) between them
+            if (pf) V2_PIECE(2, kn, sn)
+            V2_FENCE
+            X3_MMA16(acc[1], 0, 2, ah[1], al[1], bh, bl) V2_FENCE
+            if (pf) { V2_PIECE(4, kn, sn) V2_PIECE(6, kn, sn) }
+            V2_FENCE
+            X3_MMA16(acc[1], 2, 2, ah[1], al[1], bh, bl)
+            if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
+        }
+#else
         h16x8 ah0[RT], al0[RT], bh0[2], bl0[2], ah1[RT], al1[RT], bh1[2], bl1[2];
         V2_LDFRAG(0, ah0, al0, bh0, bl0)
         V2_FENCE
@@ -368,6 +514,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
             V2_MMA3(0, 1, ah1, al1, bh1, bl1)
             if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
         }
+#endif
         cur = cur == 2 ? 0 : cur + 1;
     }
 
@@ -375,17 +522,28 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     // re-reads it row-wise, so bias / residual / stores are 16-byte accesses covering whole 256-B row segments
     __syncthreads();
     if (const int ek = x3_epilogue_kind(g)) {
+#if X3_MFMA16
+        if constexpr (RT == 2) {
+            X3_EPILOGUE_SLAB(ek, g, &acc[0][0], (float*)smem + wave * (64 * 68), m0 + wm * 64, n0 + wn * 64, lane, am)
+        } else {
+            X3_EPILOGUE_HALFSLAB(ek, g, &acc[0][0], (float*)smem + wave * (32 * 68), m0 + wm * 32, n0 + wn * 64, lane, am)
+        }
+#else
         if constexpr (RT == 2) {
             X3_EPILOGUE_SLAB(ek, g, acc[0][0], acc[0][1], acc[1][0], acc[1][1], (float*)smem + wave * (64 * 68), m0 + wm * 64, n0 + wn * 64, lane, am)
         } else {
             X3_EPILOGUE_HALFSLAB(ek, g, acc[0][0], acc[0][1], acc[0][0], acc[0][1], (float*)smem + wave * (32 * 68), m0 + wm * 32, n0 + wn * 64, lane, am)
         }
+#endif
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
     {
         constexpr int ELD = 68;                                            // floats per parked row (64 + 4 pad)
         float* park = (float*)smem + wave * (32 * RT * ELD);
+#if X3_MFMA16
+        x3_park16<2 * RT>(park, &acc[0][0], lane);
+#else
 #pragma unroll
         for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -393,6 +551,7 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[i][j][r];
+#endif
         __syncthreads();
         const int c4 = (lane & 15) * 4, rsub = lane >> 4;
         const int col = n0 + wn * 64 + c4;
@@ -459,6 +618,67 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
 #define V3_ALO 16384
 #define V3_WHI 32768
 #define V3_WLO 49152
+#if X3_MFMA16
+// The ping-pong K loop of the 256-row-class kernels (v3, v3i) in the 16x16x32 shape.  With k = 32 per instruction there is no k-substep to
+// split an iteration by, so the wave's tile is split by ROW tiles: first half = 16-row tiles 0 .. MT-1, second half = MT .. 2 MT - 1, the
+// W fragments stay live across both.  The two wave groups (wm = 0 / 1: the two waves of a SIMD) run half an iteration apart; two
+// barriers per K tile (g = 2kt: tile kt has landed; g = 2kt+1); in every interval one group is in its pure-MFMA half (fragments already
+// in registers) while the other waits for its first fragments.  Both groups issue their DMA pieces of tile kt+1 in the interval
+// [2kt, 2kt+1], two behind each row tile's MFMAs (MT x 4 x 3 MFMAs of k = 32 per half: the cycles of MT x 2 x 3 of the 32x32x16 shape).
+// In scope: V3_PIECE, V3_LDA16(t0, n), V3_LDB16, V3_KT_PROLOGUE (per-iteration constants of the pieces), acc, nk, MT, SINGLE, WLO0.
+#define V3_PINGPONG16                                                                                                    \
+    h16x8 ah[2 * MT], al[2 * MT], bh[4], bl[4];                                                                          \
+    if (wm == 0) {                                                                                                       \
+        for (int kt = 0; kt < nk; ++kt) {                                                                                \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                             \
+            __builtin_amdgcn_s_barrier();                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                           \
+            V3_KT_PROLOGUE                                                                                               \
+            V3_LDB16 V3_LDA16(0, MT)                                                                                     \
+            V2_FENCE                                                                                                     \
+            _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                             \
+                X3_MMA16(acc[i], 0, 4, ah[i], al[i], bh, bl) V2_FENCE                                                    \
+                if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }                                          \
+                if (MT == 3 && i == 2 && pf) { V3_PIECE(6, kn, sn) V3_PIECE(7, kn, sn) }                                 \
+                if (i == 0) { V3_LDA16(MT, MT) }                                                                         \
+                V2_FENCE                                                                                                 \
+            }                                                                                                            \
+            __builtin_amdgcn_s_barrier();                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                           \
+            _Pragma("unroll") for (int i = 0; i < MT; ++i) { X3_MMA16(acc[MT + i], 0, 4, ah[MT + i], al[MT + i], bh, bl) V2_FENCE } \
+        }                                                                                                                \
+        __builtin_amdgcn_s_barrier();                              /* pairs with the other group's last half step */     \
+    } else {                                                                                                             \
+        for (int kt = 0; kt < nk; ++kt) {                                                                                \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                             \
+            __builtin_amdgcn_s_barrier();                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                           \
+            V3_KT_PROLOGUE                                                                                               \
+            if (kt > 0) {                                          /* second half of tile kt-1 + the DMA of tile kt+1 */ \
+                _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                         \
+                    X3_MMA16(acc[MT + i], 0, 4, ah[MT + i], al[MT + i], bh, bl) V2_FENCE                                 \
+                    if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }                                      \
+                    if (MT == 3 && i == 2 && pf) { V3_PIECE(6, kn, sn) V3_PIECE(7, kn, sn) }                             \
+                    V2_FENCE                                                                                             \
+                }                                                                                                        \
+            } else if (pf) {                                                                                             \
+                _Pragma("unroll") for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, kn, sn)                                    \
+            }                                                                                                            \
+            __builtin_amdgcn_s_barrier();                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                                           \
+            V3_LDB16 V3_LDA16(0, MT)                                                                                     \
+            V2_FENCE                                                                                                     \
+            _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                             \
+                X3_MMA16(acc[i], 0, 4, ah[i], al[i], bh, bl) V2_FENCE                                                    \
+                if (i == 0) { V3_LDA16(MT, MT) }                                                                         \
+                V2_FENCE                                                                                                 \
+            }                                                                                                            \
+        }                                                                                                                \
+        __builtin_amdgcn_s_barrier();                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                               \
+        _Pragma("unroll") for (int i = 0; i < MT; ++i) { X3_MMA16(acc[MT + i], 0, 4, ah[MT + i], al[MT + i], bh, bl) V2_FENCE } \
+    }
+#endif
 __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) {
     constexpr bool SINGLE = false;      // (separate hi / lo arrays: the plain C-ABI call, split-f16 only)
     constexpr bool WLO0 = false;
@@ -477,6 +697,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 2, wn = wave & 3, l32 = lane & 31, h = lane >> 5;
 
+#if X3_MFMA16
+    constexpr int MT = 4;
+    const int l16 = lane & 15, kq = lane >> 4;
+    (void)l32; (void)h;
+    f32x4 acc[8][4];                                // 16-row tiles x 16-column tiles of the wave's 128 x 64
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#else
     f32x16 acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -484,6 +714,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#endif
 
     // DMA: every operand tile = 256 rows x 4 chunks = 1024 chunks = 2 pieces per wave; 8 pieces per wave per stage
     size_t sa[2], sw[2];
@@ -522,6 +753,29 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #pragma unroll
         for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, 0, s0)
     }
+#if X3_MFMA16
+    const int aoff = (wm * 128 + l16) * 64, boff = (wn * 64 + l16) * 64;
+    const int co16 = (kq ^ ((l16 >> 2) & 3)) * 16;          // (the 64-byte-row image of v2: see V2_LDA16)
+#define V3_LDA16(t0, n)                                                                                                  \
+    _Pragma("unroll") for (int i_ = (t0); i_ < (t0) + (n); ++i_) {                                                       \
+        ah[i_] = *(const h16x8*)(sb + aoff + i_ * 1024 + co16);                                                          \
+        al[i_] = *(const h16x8*)(sb + V3_ALO + aoff + i_ * 1024 + co16);                                                 \
+    }
+#define V3_LDB16                                                                                                         \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                                                   \
+        bh[j_] = *(const h16x8*)(sb + V3_WHI + boff + j_ * 1024 + co16);                                                 \
+        bl[j_] = *(const h16x8*)(sb + V3_WLO + boff + j_ * 1024 + co16);                                                 \
+    }
+#define V3_KT_PROLOGUE                                                                                                   \
+    const bool pf = kt + 1 < nk;                                                                                         \
+    const int kn = (kt + 1) * g.kstep;                                                                                   \
+    char* sn = smem + ((kt + 1) & 1) * V3_STAGE;                                                                         \
+    const char* sb = smem + (kt & 1) * V3_STAGE;
+    V3_PINGPONG16
+#undef V3_LDA16
+#undef V3_LDB16
+#undef V3_KT_PROLOGUE
+#else
     const int swz = (l32 >> 2) & 3;
     const int aoff = (wm * 128 + l32) * 64, boff = (wn * 64 + l32) * 64;
     // Ping-pong: the two waves of a SIMD belong to the row groups wm = 0 / 1, which run the same K loop half an iteration apart.
@@ -589,6 +843,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #pragma unroll
         for (int i = 0; i < 4; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
     }
+#endif
     // epilogue through LDS, two passes of 64 rows per wave (8 waves x 64 x 68 floats = 139 KB)
     constexpr int ELD = 68;
     float* park = (float*)smem + wave * (64 * ELD);
@@ -600,12 +855,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
+#if X3_MFMA16
+        x3_park16<4>(park, &acc[half * 4][0], lane);
+#else
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[half * 2 + i][j][r];
+#endif
         __syncthreads();
         if (col < g.N) {
             const float osd_ = g.Chi ? x3_out_scale(g) : 1.0f;   // scale of the split output, read BEFORE the first store of the loop (exactly 1 when none: v * 1 == v)
@@ -744,6 +1003,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 2, wn = wave & 3, l32 = lane & 31, h = lane >> 5;
 
+#if X3_MFMA16
+    const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 16-byte k chunk of this lane
+    (void)l32; (void)h;
+    f32x4 acc[2 * MT][4];                           // 16-row tiles x 16-column tiles of the wave's (32 MT) x 64
+#pragma unroll
+    for (int i = 0; i < 2 * MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#else
     f32x16 acc[MT][2];
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -751,6 +1019,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#endif
 
     // DMA: every operand tile = 256 rows x 4 chunks = 1024 chunks = 2 pieces per wave; 8 pieces per wave per stage
     // Interleaved operands: row r of A (and W) holds, per K tile, one 128-byte block [32 hi | 32 lo]; a DMA instruction moves 8 rows
@@ -838,6 +1107,45 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
         for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, 0, s0)
     }
+#if X3_MFMA16
+    // 16x16x32 fragments: lane l reads hi chunk l >> 4, or lo chunk 4 + (l >> 4), of row base + (l & 15) (base a multiple of 16, so the
+    // row's swizzle is (l & 15) >> 1): a 16-lane ds_read_b128 group reads 16 consecutive rows of one chunk — the case the slot
+    // swizzle above makes conflict-free.  2 MT A row tiles x (hi, lo) + 4 W column tiles x (hi, lo) reads per wave and K tile.
+    const int swz = l16 >> 1;
+    const int aoff = (wm * (MT * 32) + l16) * 128, boff = (wn * 64 + l16) * 128;
+    const int ch16 = (kq ^ swz) * 16, cl16 = ((4 + kq) ^ swz) * 16;
+#define V3_LDA16(t0, n)                                                                                                  \
+    _Pragma("unroll") for (int i_ = (t0); i_ < (t0) + (n); ++i_) {                                                       \
+        ah[i_] = *(const h16x8*)(sb + aoff + i_ * 2048 + ch16);                                                          \
+        al[i_] = *(const h16x8*)(sb + aoff + i_ * 2048 + cl16);                                                          \
+    }
+#define V3_LDB16                                                                                                         \
+    {                                                                                                                    \
+        if constexpr (WLO0 == 2) {                                                                                       \
+            /* K tile kt = half (kt & 1) of its pair's 128-byte rows (chunks 0-3 / 4-7), in the W buffer of the pair's parity */ \
+            const int cp_ = (((kt & 1) * 4 + kq) ^ swz) * 16;                                                            \
+            const char* sw_ = smem + ((kt >> 1) & 1) * V3_STAGE + 32768 + boff;                                          \
+            _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) { bh[j_] = *(const h16x8*)(sw_ + j_ * 2048 + cp_); bl[j_] = bh[j_]; } \
+        } else {                                                                                                         \
+            _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                                           \
+                bh[j_] = *(const h16x8*)(sb + 32768 + boff + j_ * 2048 + ch16);                                          \
+                bl[j_] = *(const h16x8*)(sb + 32768 + boff + j_ * 2048 + cl16);                                          \
+            }                                                                                                            \
+        }                                                                                                                \
+    }
+#define V3_KT_PROLOGUE                                                                                                   \
+    const bool pf = kt + 1 < nk;                                                                                         \
+    const int kn = (kt + 1) * g.kstep;                                                                                   \
+    const bool wnext_ = ((kt + 1) & 1) == 0; const int kkw_ = ((kt + 1) >> 1) * 64, wb_ = ((kt + 1) >> 1) & 1;      /* (WLO0 == 2) */ \
+    (void)wnext_; (void)kkw_; (void)wb_;                                                                                 \
+    if constexpr (CONV) { if (pf) coff_ = conv_off(kt + 1, ctap_); }                                                     \
+    char* sn = smem + ((kt + 1) & 1) * V3_STAGE;                                                                         \
+    const char* sb = smem + (kt & 1) * V3_STAGE;
+    V3_PINGPONG16
+#undef V3_LDA16
+#undef V3_LDB16
+#undef V3_KT_PROLOGUE
+#else
     const int swz = (l32 >> 1) & 7;
     const int aoff = (wm * (MT * 32) + l32) * 128, boff = (wn * 64 + l32) * 128;
     // Ping-pong: the two waves of a SIMD belong to the row groups wm = 0 / 1, which run the same K loop half an iteration apart.
@@ -913,6 +1221,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
         for (int i = 0; i < MT; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
     }
+#endif
     if constexpr (SK) {
         const int nk_full = g.K / X3_BK;
         if (k1 < nk_full) {
@@ -921,8 +1230,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
             const auto rs = __builtin_amdgcn_make_buffer_rsrc((char*)g.sk_ws + (size_t)gid * X3_SK_SLAB_BYTES, 0, X3_SK_SLAB_BYTES, 0x00020000);
 #pragma unroll
             for (int q = 0; q < 32; ++q) {
+#if X3_MFMA16
+                const f32x4 v_ = acc[q >> 2][q & 3];                    // (register layout of THIS build: written and read by the same kernel)
+#else
                 const f32x16& a_ = acc[q >> 3][(q >> 2) & 1];
                 const f32x4 v_ = {a_[(q & 3) * 4], a_[(q & 3) * 4 + 1], a_[(q & 3) * 4 + 2], a_[(q & 3) * 4 + 3]};
+#endif
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v_), rs, (q * 512 + t) * 16, 0, 16 /* sc1: write-through */);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // EVERY storing wave drains its stores ...
@@ -953,8 +1266,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
                 for (int u = 0; u < 8; ++u) {
                     const int q = q8 * 8 + u;
                     const f32x4 f_ = __builtin_bit_cast(f32x4, v_[u]);
+#if X3_MFMA16
+                    acc[q >> 2][q & 3] += f_;
+#else
                     f32x16& a_ = acc[q >> 3][(q >> 2) & 1];
                     a_[(q & 3) * 4] += f_[0]; a_[(q & 3) * 4 + 1] += f_[1]; a_[(q & 3) * 4 + 2] += f_[2]; a_[(q & 3) * 4 + 3] += f_[3];
+#endif
                 }
             }
         }
@@ -964,11 +1281,19 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
         __syncthreads();
         // (written out, not a `#pragma unroll` loop over the halves: with every epilogue kind inlined the loop body exceeds the pragma-unroll
         //  size limit once the pair kinds carry the line-complete stores — the loop then stays a loop and acc[half * 2] becomes scratch)
+#if X3_MFMA16
+        X3_EPILOGUE_SLAB(ek, g, &acc[0][0], parkf, m0 + wm * (MT * 32), n0 + wn * 64, lane, am)              // 16-row tiles 0-3
+        if constexpr (MT == 4)
+            X3_EPILOGUE_SLAB(ek, g, &acc[4][0], parkf, m0 + wm * (MT * 32) + 64, n0 + wn * 64, lane, am)
+        if constexpr (MT == 3)           // 16-row tiles 4-5: half a slab
+            X3_EPILOGUE_HALFSLAB(ek, g, &acc[4][0], parkf, m0 + wm * 96 + 64, n0 + wn * 64, lane, am)
+#else
         X3_EPILOGUE_SLAB(ek, g, acc[0][0], acc[0][1], acc[1][0], acc[1][1], parkf, m0 + wm * (MT * 32), n0 + wn * 64, lane, am)
         if constexpr (MT == 4)
             X3_EPILOGUE_SLAB(ek, g, acc[2][0], acc[2][1], acc[3][0], acc[3][1], parkf, m0 + wm * (MT * 32) + 64, n0 + wn * 64, lane, am)
         if constexpr (MT == 3)           // the third 32-row tile: half a slab
             X3_EPILOGUE_HALFSLAB(ek, g, acc[2][0], acc[2][1], acc[2][0], acc[2][1], parkf, m0 + wm * 96 + 64, n0 + wn * 64, lane, am)
+#endif
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
@@ -983,6 +1308,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
+#if X3_MFMA16
+        if (half == 0) x3_park16<4>(park, &acc[0][0], lane);
+        else x3_park16<2 * MT - 4>(park, &acc[4][0], lane);
+#else
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -990,6 +1319,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if (half * 2 + i < MT) park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[half * 2 + i < MT ? half * 2 + i : 0][j][r];
+#endif
         __syncthreads();
         if (col < g.N) {
             const float osd_ = g.Chi ? x3_out_scale(g) : 1.0f;   // scale of the split output, read BEFORE the first store of the loop (exactly 1 when none: v * 1 == v)

@@ -3,6 +3,13 @@
 #pragma once
 #include "kernels.h"
 
+// MFMA shape of the split-f16 kernel family (gemm_f16x3.hip: the register-staged kernel, v2, v3, v3i): 1 = v_mfma_f32_16x16x32_f16, one
+// instruction per product and 32-wide K block; 0 = v_mfma_f32_32x32x16_f16, two k-substeps of 16 (`make X3_MFMA16=0`: the A/B partner).
+// Compile time only: the two shapes sum inside the instruction in different orders, so every kernel of the family moves together.
+#ifndef X3_MFMA16
+#define X3_MFMA16 1
+#endif
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -101,11 +108,10 @@ __device__ __forceinline__ void x3_publish_scale(const GemmX3Args& g) {
 // One call = the 64x64 slab of one wave: a0..a3 = accumulator tiles (i, j) = (0,0) (0,1) (1,0) (1,1); row0 / col0 = its origin.
 // LEAN (the experimental 4-wave kernel, which has no register to spare): the forward towers' form only -- host alpha, no ReLU, no
 // max|C|, no output scale
-template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN = false, int NIT = 16>
-__device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x16& a0, const f32x16& a1, const f32x16& a2, const f32x16& a3,
-                                                 float* park, int row0, int col0, int lane, float& am) {
+// The PARK step alone depends on the accumulator layout (parkfn: the two overloads of x3_epilogue_slab below).
+template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN, int NIT, class PARKFN>
+__device__ __forceinline__ void x3_epilogue_slab_impl(const GemmX3Args& g, const PARKFN& parkfn, float* park, int row0, int col0, int lane, float& am) {
     constexpr int ELD = 68;
-    const int l32 = lane & 31, h = lane >> 5;
     const int c4 = (lane & 15) * 4, rsub = lane >> 4;
     const int col = col0 + c4;
     const bool colok = col < g.N;
@@ -127,12 +133,7 @@ __device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x
 #pragma unroll
         for (int it = 0; it < NIT; ++it) rr[it] = *(const float4*)(g.residual + (size_t)min(rbase + it * 4, g.M - 1) * g.ldr + colc);
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int pr = mfma32_row(r, h) * ELD + l32;
-        park[pr] = a0[r]; park[pr + 32] = a1[r];
-        if constexpr (NIT == 16) { park[pr + 32 * ELD] = a2[r]; park[pr + 32 * ELD + 32] = a3[r]; }        // (NIT = 8: a 32-row half slab, a0 / a1 only)
-    }
+    parkfn();
     // Round 6: LINE-COMPLETE pair stores (kinds 3 / 4: in_proj -> Q / K / V pairs, c_fc + QuickGELU -> pairs; interleaved layout, 64 whole columns).
     // A lane holds 4 columns of a row; its hi halves (8 B) and lo halves (8 B) used to go out as two instructions that each wrote HALF of
     // every 128-byte line they touched ([hi c0-31 | lo c0-31] per 32-column block): every line requested twice, 256 line requests per 64x64
@@ -220,6 +221,38 @@ __device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x
         }
         asm volatile("" ::: "memory");
     }
+}
+// 32x32 accumulator tiles: a0..a3 = tiles (i, j) = (0,0) (0,1) (1,0) (1,1) of the slab
+template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN = false, int NIT = 16>
+__device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x16& a0, const f32x16& a1, const f32x16& a2, const f32x16& a3,
+                                                 float* park, int row0, int col0, int lane, float& am) {
+    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, LEAN, NIT>(g, [&]() {
+        constexpr int ELD = 68;
+        const int l32 = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int pr = mfma32_row(r, h) * ELD + l32;
+            park[pr] = a0[r]; park[pr + 32] = a1[r];
+            if constexpr (NIT == 16) { park[pr + 32 * ELD] = a2[r]; park[pr + 32 * ELD + 32] = a3[r]; }        // (NIT = 8: a 32-row half slab, a0 / a1 only)
+        }
+    }, park, row0, col0, lane, am);
+}
+// 16x16 accumulator tiles (v_mfma_f32_16x16x32: column = lane & 15, row = 4 (lane >> 4) + register): a[ti * 4 + tj] = tile (ti, tj) of NT
+// row tiles x 4 column tiles.  With ELD = 68 the 64 lanes of one store fall in banks 16 (lane >> 4) + (lane & 15): all distinct.
+template <int NT>
+__device__ __forceinline__ void x3_park16(float* park, const f32x4* a, int lane) {
+    constexpr int ELD = 68;
+    float* p = park + (4 * (lane >> 4)) * ELD + (lane & 15);
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[(16 * ti + r) * ELD + 16 * tj] = a[ti * 4 + tj][r];
+}
+template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN = false, int NIT = 16>
+__device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x4* a, float* park, int row0, int col0, int lane, float& am) {
+    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, LEAN, NIT>(g, [&]() { x3_park16<NIT / 4>(park, a, lane); }, park, row0, col0, lane, am);
 }
 // which specialisation (wave-uniform): 0 = none (generic epilogue), 1 = f32 out, 2 = f32 out + residual, 3 = QuickGELU -> operand pair,
 // 4 = operand pair only (in_proj of the image towers: Q / K / V go to the attention kernel as f16 pairs, attention_pair.hip)
