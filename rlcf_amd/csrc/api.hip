@@ -108,20 +108,8 @@ static int gemm_f16x3_call(const void* Ahi, const void* Alo, int lda, const void
                            const float* residual, int ldr, const float* aux, int ldaux, float* C, int ldc, void* Chi, void* Clo, int ldch,
                            int M, int N, int K, float alpha, int epilogue, rlcf_stream stream, int single) {
     RLCF_ARG_CHECK(epilogue >= RLCF_EPI_NONE && epilogue <= RLCF_EPI_RELU && (epilogue != RLCF_EPI_QUICKGELU_BWD || aux));
-    hipStream_t st = (hipStream_t)stream;
-    // stateless call: the stream-K scratch of the 256x256 kernel (grids of >= 64 tiles that do not fill their last round) comes from
-    // the stream-ordered allocator; the engine path owns its own (engine.h: gemm_ws)
-    const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-    char* ws = nullptr;
-    unsigned epoch = 0;
-    static int sk_on = -1;                                   // (off by default: gemm_f16x3.hip says why)
-    if (sk_on < 0) { const char* ev = getenv("RLCF_X3_SK"); sk_on = ev ? atoi(ev) : 0; }
-    if (sk_on && tiles >= 64 && tiles % 256 != 0 && (const char*)Alo == (const char*)Ahi + 64) RLCF_HIP_CHECK(hipMallocAsync((void**)&ws, X3_WS_BYTES, st));
-    const int rc = launch_gemm_f16x3(Ahi, Alo, lda, Whi, Wlo, ldw, bias, residual, ldr, aux, ldaux, C, ldc, Chi, Clo, ldch, M, N, K, alpha,
-                                     epilogue, st, nullptr, nullptr, 0, (float*)ws,
-                                     ws ? X3_WS_BYTES : 0, single, nullptr, ws ? &epoch : nullptr);
-    if (ws) (void)hipFreeAsync(ws, st);
-    return rc;
+    return launch_gemm_f16x3(Ahi, Alo, lda, Whi, Wlo, ldw, bias, residual, ldr, aux, ldaux, C, ldc, Chi, Clo, ldch, M, N, K, alpha,
+                             epilogue, (hipStream_t)stream, nullptr, nullptr, 0, nullptr, 0, single);
 }
 int rlcf_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi, const void* Wlo, int ldw, const float* bias,
                     const float* residual, int ldr, const float* aux, int ldaux, float* C, int ldc, void* Chi, void* Clo, int ldch,

@@ -206,11 +206,10 @@ struct rlcf_engine {
     DevBuf dyn;                      // {max|A|, s, 1/s} of a dynamically scaled split (ResNet activations)
     DevBuf a_hi;                     // interleaved split copy of the current GEMM A operand (F16X3 mode)
     size_t a_split_elems = 0;
-    DevBuf gemm_ws;                  // split-K workspace of the small-grid split-f16 GEMM (X3_SPLITK_WS_BYTES, sized at create)
+    DevBuf gemm_ws;                  // split-K workspace of the small-grid split-f16 GEMM (X3_WS_BYTES, sized at create)
     // one-image calls: the reward models' tower pass of the selected views runs on a second stream next to the student's sparse text
     // forward (both leave most of the 256 CUs idle at one image's sizes); fork / join by events, its own split-K workspace
     DevBuf gemm_ws2;
-    unsigned ws_epoch[2] = {0, 0};   // stream-K launch counters of gemm_ws / gemm_ws2 (gemm_f16x3.hip: flags carry the launch's epoch)
     // ... its own copies of the image-tower scratch (engine_encode_image on the side stream: the reward models' pass of one part of a
     // sample batch runs beside the student tower of the next part, tta_batch_pipelined) ...
     // norm-layer tuning of a ModifiedResNet student: running statistics of every BatchNorm2d (reset per sample, updated by train-mode

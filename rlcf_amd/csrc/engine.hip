@@ -55,7 +55,6 @@ static void prof_end(int slot, hipStream_t st, int kind = 0) {
 // part reaches 25.8 B/clk/CU, a 128-B one 45.5: profiles/r1_gemm_sq_counters.txt).  The lo part of a pair therefore starts 64 B after hi.
 static inline float* ws_ptr(rlcf_engine* e) { return (e->ws_sel ? e->gemm_ws2 : e->gemm_ws).as<float>(); }
 static inline size_t ws_bytes(rlcf_engine* e) { return (e->ws_sel ? e->gemm_ws2 : e->gemm_ws).bytes; }
-static inline unsigned* ws_epoch(rlcf_engine* e) { return &e->ws_epoch[e->ws_sel ? 1 : 0]; }
 // image-tower scratch / A-operand split buffer of the stream whose launches are being enqueued (see ws_sel)
 #define IMG_BUF(e, name) ((e)->ws_sel ? (e)->side_img.name : (e)->name)
 static inline void* a_ptr(rlcf_engine* e) { return e->ws_sel ? e->a_hi2.p : e->a_hi.p; }
@@ -102,7 +101,7 @@ static int gemm(rlcf_engine* e, const float* A, int lda, const float* W, int ldw
             if (sp->lo_zero && sp->hi_only) gemm_f16x3_next_packed_w(sp->hi_only);
             int rc = launch_gemm_f16x3(a_ptr(e), lo_of(a_ptr(e)), 2 * K, sp->hi, sp->lo, 2 * K, bias, res, ldr, aux, ldaux, C, ldc, nullptr,
                                        nullptr, 0, M, N, K, alpha * sp->inv_scale / a_scale, epi, st, alpha_dev, amax_out, 0,
-                                       ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr, ws_epoch(e));
+                                       ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr);
             prof_end(slot, st, g_last_x3_variant);
             return rc;
         }
@@ -120,7 +119,7 @@ static int gemm(rlcf_engine* e, const float* A, int lda, const float* W, int ldw
             TRY(e->dyn.ensure(3 * sizeof(float)));
             const int slot = prof_begin(st, 2.0 * M * N * K, M, N, K);
             int rc = launch_gemm_skinny_x3(A, lda, sp->hi, bias, res, ldr, aux, ldaux, C, ldc, M, N, K, alpha * sp->inv_scale, epi,
-                                           dyn_scale ? amax_in : nullptr, amax_out, ws_ptr(e), ws_bytes(e) - X3_SK_FLAG_BYTES_RESERVED,
+                                           dyn_scale ? amax_in : nullptr, amax_out, ws_ptr(e), ws_bytes(e),
                                            e->dyn.as<float>() + 2, st, dyn_scale && !amax_in);
             prof_end(slot, st, g_last_x3_variant);
             return rc;
@@ -147,7 +146,7 @@ int engine_gemm_presplit(rlcf_engine* e, const float* W, const float* bias, cons
     const int slot = prof_begin(st, 2.0 * M * N * K, M, N, K);
     if (sp->lo_zero && sp->hi_only) gemm_f16x3_next_packed_w(sp->hi_only);
     int rc = launch_gemm_f16x3(a_ptr(e), lo_of(a_ptr(e)), 2 * K, sp->hi, sp->lo, 2 * K, bias, res, ldr, nullptr, 0, C, ldc, nullptr, nullptr, 0, M, N, K,
-                               sp->inv_scale, epi, st, alpha_dev, (unsigned int*)amax_out, 0, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr, ws_epoch(e));
+                               sp->inv_scale, epi, st, alpha_dev, (unsigned int*)amax_out, 0, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr);
     prof_end(slot, st, g_last_x3_variant);
     return rc;
 }
@@ -164,7 +163,7 @@ int engine_gemm_pairs(rlcf_engine* e, const void* Apairs, int K, const float* al
     const int slot = prof_begin(st, 2.0 * M * N * K, M, N, K);
     if (sp->lo_zero && sp->hi_only) gemm_f16x3_next_packed_w(sp->hi_only);
     int rc = launch_gemm_f16x3(Apairs, lo_of(Apairs), 2 * K, sp->hi, sp->lo, 2 * K, bias, res, ldr, nullptr, 0, C, ldc, Cpairs, Cpairs ? lo_of(Cpairs) : nullptr,
-                               2 * N, M, N, K, sp->inv_scale, epi, st, alpha_dev, (unsigned int*)amax_out, 1, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, out_scale_dev, ws_epoch(e));
+                               2 * N, M, N, K, sp->inv_scale, epi, st, alpha_dev, (unsigned int*)amax_out, 1, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, out_scale_dev);
     prof_end(slot, st, g_last_x3_variant);
     return rc;
 }
@@ -221,7 +220,7 @@ static int gemm_pre(rlcf_engine* e, const void* A2, int lda, const float* W, con
         if (!fw || K % 64) { rlcf_set_error("gemm_pre: weight has no plain f16 copy (K = %d)", K); return RLCF_ERR_STATE; }
         const int slot = prof_begin(st, 2.0 * M * N * K, M, N, K);
         int rc = launch_gemm_f16x3(A2, lo_of(A2), lda, fw->hi, lo_of(fw->hi), K, bias, res, ldr, nullptr, 0, C, ldc, C2, nullptr, ldch, M, N, K,
-                                   fw->inv_scale, epi, st, nullptr, nullptr, 0, ws_ptr(e), ws_bytes(e), 1, nullptr, ws_epoch(e));
+                                   fw->inv_scale, epi, st, nullptr, nullptr, 0, ws_ptr(e), ws_bytes(e), 1, nullptr);
         prof_end(slot, st, g_last_x3_variant);
         return rc;
     }
@@ -230,7 +229,7 @@ static int gemm_pre(rlcf_engine* e, const void* A2, int lda, const float* W, con
     const int slot = prof_begin(st, 2.0 * M * N * K, M, N, K);
     if (sp->lo_zero && sp->hi_only) gemm_f16x3_next_packed_w(sp->hi_only);
     int rc = launch_gemm_f16x3(A2, lo_of(A2), 2 * lda, sp->hi, sp->lo, 2 * K, bias, res, ldr, nullptr, 0, C, ldc, C2, C2 ? lo_of(C2) : nullptr,
-                               2 * ldch, M, N, K, sp->inv_scale, epi, st, nullptr, nullptr, 1, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr, ws_epoch(e));
+                               2 * ldch, M, N, K, sp->inv_scale, epi, st, nullptr, nullptr, 1, ws_ptr(e), ws_bytes(e), sp->lo_zero ? 2 : 0, nullptr);
     prof_end(slot, st, g_last_x3_variant);
     return rc;
 }
@@ -638,7 +637,7 @@ static int wgrad(rlcf_engine* e, const float* dY, int ldy, int N, const float* X
         const int slot = prof_begin(st, 2.0 * N * K * Tp, N, K, Tp);
         rc = launch_gemm_f16x3(e->a_hi.p, lo_of(e->a_hi.p), 2 * Tp, e->w_hi.p, lo_of(e->w_hi.p), 2 * Tp, nullptr, nullptr, 0, nullptr, 0, dW, K,
                                nullptr, nullptr, 0, N, K, Tp, 1.f, RLCF_EPI_NONE, st, e->dyn.as<float>() + 2, nullptr, 0, ws_ptr(e),
-                               ws_bytes(e), 0, nullptr, ws_epoch(e));
+                               ws_bytes(e), 0, nullptr);
         prof_end(slot, st, g_last_x3_variant);
     } else {
         GemmArgs g{};

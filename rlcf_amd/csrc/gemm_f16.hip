@@ -281,9 +281,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16_pp_kernel(GemmX3Args g) {
     // of stores — would hit the fabric in the same ~4 us of every tile round, and the next tile's first loads queue behind them (s_memtime
     // trace: the K loop after a store burst runs 20 % slower per K tile than in the middle of a long tile).  Cohort c of P (by the
     // workgroup's index inside its XCD) therefore starts c / P of a tile late: the bursts of the cohorts interleave with the others' K loops.
-    if (g.sk_blocks > 1 || g.sk_blocks < -1) {
-        const int P = g.sk_blocks > 0 ? g.sk_blocks : -g.sk_blocks;
-        const int c = g.sk_blocks > 0 ? widx % P : xcd % P;                 // (negative: whole XCDs as cohorts — their workgroups stay in step)
+    if (g.pp_desync > 1 || g.pp_desync < -1) {
+        const int P = g.pp_desync > 0 ? g.pp_desync : -g.pp_desync;
+        const int c = g.pp_desync > 0 ? widx % P : xcd % P;                 // (negative: whole XCDs as cohorts — their workgroups stay in step)
         const int cyc = c * (nk * 2800 + 6000) / P;              // ~ cycles per tile: 8 intervals of ~350 per K tile + epilogue
         for (int q = cyc >> 10; q > 0; --q) __builtin_amdgcn_s_sleep(16);            // (s_sleep counts 64-cycle units)
     }
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16_pp_kernel(GemmX3Args g) {
     }
 #define PP_NOHOOK(n)
 #define PP_WAIT_PP_NOHOOK asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-#define PP_ST(v, p) { if (g.sk_epoch) __builtin_nontemporal_store(v, (h16x8*)(p)); else *(h16x8*)(p) = v; }      // (g.sk_epoch: RLCF_F16_PP_NT)
+#define PP_ST(v, p) { if (g.pp_nt) __builtin_nontemporal_store(v, (h16x8*)(p)); else *(h16x8*)(p) = v; }      // (g.pp_nt: RLCF_F16_PP_NT)
 // K tile 0 of a tile (round 5).  Stores count in vmcnt like loads and retire in order, and the epilogue's 16 stores per wave take
 // ~6 us to retire when every CU of the chip bursts its 128-KB tile at the same moment (without stores in_proj runs 818 instead of
 // 1031 us, c_fc 1023 instead of 1363: profiles/r5_notes.md) — whatever load the NEXT wait covers that was issued AFTER them waits for
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16_pp_kernel(GemmX3Args g) {
     };
     auto rs_pend = rsrc_out(0, 0);
     bool have_pend = false;                      // (wave-uniform: set by the epilogue of a whole tile that has a successor)
-    const bool can_defer = DEFER && nk >= 12 && g.ksplit == 0 && !g.sk_epoch && (size_t)256 * g.ldch * 2 < 0xfffff000u;
+    const bool can_defer = DEFER && nk >= 12 && g.ksplit == 0 && !g.pp_nt && (size_t)256 * g.ldch * 2 < 0xfffff000u;
 // (TRACE is its own instantiation: the stamp code costs the production kernel registers it needs for the deferred stores)
 #define PP_STAMP(k) if constexpr (TRACE != 0) { if (trace && (wave & 3) == 0 && lane == 0 && tile_it < 64) trace[(((size_t)blockIdx.x * 64 + tile_it) * 2 + wm) * 16 + (k)] = __builtin_amdgcn_s_memtime(); }
     for (;;) {
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16_pp_kernel(GemmX3Args g) {
             const bool inside = m0 + 256 <= g.M && n0 + 256 <= g.N && (g.ldch & 7) == 0;       // (whole tile, 16-byte aligned rows: no masks)
             _Float16* obase = g.Chi + (size_t)orow * g.ldch + ocol;
             const bool defer_now = DEFER && can_defer && inside && have_next;
-            const bool bufst = inside && (!g.sk_epoch || TS != 0) && (size_t)256 * g.ldch * 2 < 0xfffff000u;      // (RLCF_F16_PP_NT: the whole-line path carries its own nt form)
+            const bool bufst = inside && (!g.pp_nt || TS != 0) && (size_t)256 * g.ldch * 2 < 0xfffff000u;      // (RLCF_F16_PP_NT: the whole-line path carries its own nt form)
             auto rs_out = rsrc_out(m0, n0);
             if constexpr (DEFER != 0) {
                 if (defer_now) rs_pend = rs_out;
@@ -649,7 +649,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16_pp_kernel(GemmX3Args g) {
                                        "v"(__builtin_bit_cast(u32x4, oq[3])), "v"(ts_r0)
                                      : "memory");
                         const int so = (i * 32) * g.ldch * 2;
-                        if (g.sk_epoch) {                                  // RLCF_F16_PP_NT: the cache-policy operand is an immediate (2 = nt)
+                        if (g.pp_nt) {                                  // RLCF_F16_PP_NT: the cache-policy operand is an immediate (2 = nt)
                             __builtin_amdgcn_raw_buffer_store_b128(t0, rs_out, ts_v0, so, 2);
                             __builtin_amdgcn_raw_buffer_store_b128(t1, rs_out, ts_v0, so + 8 * g.ldch * 2, 2);
                             __builtin_amdgcn_raw_buffer_store_b128(t2, rs_out, ts_v0, so + 16 * g.ldch * 2, 2);
@@ -732,7 +732,7 @@ int launch_gemm_f16_pp_ln(const void* A, int lda, const void* W, int ldw, const 
     RLCF_ARG_CHECK((size_t)256 * lda * 2 < 0x7fffffffu && (size_t)256 * ldw * 2 < 0x7fffffffu && (((uintptr_t)ln_s) & 15) == 0 && (((uintptr_t)bias) & 15) == 0);
     GemmX3Args g{};
     g.Ahi = (const _Float16*)A; g.lda = lda; g.Whi = (const _Float16*)W; g.ldw = ldw; g.bias = bias; g.Chi = (_Float16*)out16; g.ldch = ldo;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.epilogue = epilogue; g.kstep = 64; g.ksplit = 0; g.tile_group = 0; g.sk_blocks = 1;
+    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.epilogue = epilogue; g.kstep = 64; g.ksplit = 0; g.tile_group = 0; g.pp_desync = 1;
     g.ln_mr = ln_mr; g.ln_s = ln_s; g.ln_part = ln_part;
     static int ncu = 0;
     if (!ncu) {
@@ -746,7 +746,7 @@ int launch_gemm_f16_pp_ln(const void* A, int lda, const void* W, int ldw, const 
     const size_t shp = (size_t)2 * P8_PAR + 8 * 4096;      // + a 4-KB slab per wave (bias slice; TS: the transposing epilogue)
     const char* tse = getenv("RLCF_F16_PP_TSTORE");          // (mode 1: full-line stores through the per-wave LDS slab, as the plain products)
     const bool tstore = (tse ? atoi(tse) : 1) != 0;
-    g.sk_epoch = pp_nt_for(tstore && mode == 1);
+    g.pp_nt = pp_nt_for(tstore && mode == 1);
 #define PP_LN_GO(E, MD, S)                                                                                                          \
     {                                                                                                                               \
         int rc = rlcf_func_lds((const void*)gemm_nt_f16_pp_kernel<E, MD, 0, 0, S>, shp);                                             \
@@ -785,7 +785,7 @@ int launch_gemm_f16_p8(const void* A, int lda, const void* W, int ldw, const flo
         g.ksplit = abl;
         static int desync = -1;                              // RLCF_F16_PP_DESYNC=P: start-time cohorts (1 = all together)
         if (desync < 0) { const char* e = getenv("RLCF_F16_PP_DESYNC"); desync = e ? atoi(e) : 1; }
-        g.sk_blocks = blocks > grid ? desync : 1;            // (one tile per workgroup: nothing to interleave)
+        g.pp_desync = blocks > grid ? desync : 1;            // (one tile per workgroup: nothing to interleave)
         // RLCF_F16_PP_TRACE=1 (measurement): stamp buffer, dumped after every launch (synchronises: not for timing runs)
         static int trace_on = -1;
         static unsigned long long* trace_buf = nullptr;
@@ -804,7 +804,7 @@ int launch_gemm_f16_p8(const void* A, int lda, const void* W, int ldw, const flo
         // RLCF_F16_PP_TSTORE (read per launch): 1 = full-line stores through the per-wave LDS slab (TS), 0 = 32 rows x 32 B per instruction
         const char* tse = getenv("RLCF_F16_PP_TSTORE");
         const bool tstore = (tse ? atoi(tse) : 1) != 0 && !defer && abl == 0;
-        g.sk_epoch = pp_nt_for(tstore);
+        g.pp_nt = pp_nt_for(tstore);
 #define PP_GO(E, D, T, S)                                                                                                           \
     {                                                                                                                               \
         int rc = rlcf_func_lds((const void*)gemm_nt_f16_pp_kernel<E, 0, D, T, S>, shp);                                              \

@@ -6,14 +6,12 @@
 // as  ahi*bhi + ahi*blo + alo*bhi  with THREE MFMAs into ONE f32 accumulator (each f16 x f16 product is
 // exact in f32); the dropped lo*lo term is 2^-22 relative.
 //
-// INVARIANT of the kernel family (gemm_nt_f16x3_kernel, _v2, _v3, _v3i; X3_MFMA16 = 1, the default build):
+// INVARIANT of the kernel family (gemm_nt_f16x3_kernel, _v2, _v3, _v3i):
 //   Per output element and per 32-wide K block, ONE v_mfma_f32_16x16x32_f16 per product (k = 32), in the order hi.hi, hi.lo, lo.hi,
 //   K blocks in increasing order.
 // (SINGLE: hi.hi, lo.lo; WLO0: the middle product dropped.)  Whichever kernel the launcher picks for a product therefore gives the
-// same bits.  `make X3_MFMA16=0` builds the family on v_mfma_f32_32x32x16_f16 instead (two k-substeps of 16 per K block, the three
-// products per substep): the two shapes sum inside the instruction in different orders, so the family moves as a whole and the
-// shape is a compile-time constant (gemm_x3.h), never a run-time choice.  gemm_skinny_x3_kernel (launch-bound, its own operand
-// scaling) and the experimental gemm_nt_f16x3_v4_kernel stay on 32x32x16 in both builds.
+// same bits.  An MFMA shape sums inside the instruction in its own order, so the family keeps ONE shape: a change of shape moves every
+// kernel of it together.  gemm_skinny_x3_kernel (launch-bound, its own operand scaling) is not of the family: it runs on 32x32x16.
 // Fragment map of 16x16x32: lane l holds row (column) l & 15, k = 8 (l >> 4) + j of the K block; C/D: column l & 15, row 4 (l >> 4) + reg.  Measured on the ViT-B/16 image tower the
 // feature error vs f64 is 6.9e-8 (plain f32: 6.1e-8, plain f16: 5.3e-5, bf16: 4.7e-4), i.e. the
 // 1e-3 logit tolerance of the RLCF parity contract holds with the margin of the f32 path while
@@ -35,7 +33,6 @@
 #define X3_LD 40                        // halves per LDS row (32 + 8 pad = 80 B)
 #define X3_TILE (X3_BM * X3_LD)         // halves per operand tile
 
-#if X3_MFMA16
 __device__ __forceinline__ f32x4 x3_mfma16(h16x8 a, h16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // One 16-row tile (fragments AH / AL) against the 16-column tiles [c0, c0 + NC) of the wave (BH[] / BL[]), into ACC[] (f32x4 per column
 // tile), PASS BY PASS: no MFMA directly follows its predecessor on the same accumulator, and each accumulator takes hi.hi, hi.lo,
@@ -52,7 +49,6 @@ __device__ __forceinline__ f32x4 x3_mfma16(h16x8 a, h16x8 b, f32x4 c) { return _
             _Pragma("unroll") for (int j_ = (c0); j_ < (c0) + (NC); ++j_) ACC[j_] = x3_mfma16(AL, BH[j_], ACC[j_]);      \
         }                                                                                                                \
     }
-#endif
 
 template <bool SINGLE>
 __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
@@ -70,26 +66,15 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
     const int tile_m = bid / tiles_n, tile_n = bid % tiles_n;
     const int m0 = tile_m * X3_BM, n0 = tile_n * X3_BN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
 
-#if X3_MFMA16
     constexpr bool WLO0 = false;
     const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 8-wide k group of this lane
-    (void)l32; (void)h;
     f32x4 acc[4][4];                                // 16-row tiles x 16-column tiles of the wave's 64 x 64
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
 
     // staging: each operand tile = 128 rows x 64 B = 512 16-B chunks, 2 per thread (rows r0 and r0+64)
     const int r0 = t >> 2, c8 = (t & 3) * 8;
@@ -117,19 +102,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
     X3_GLOAD(0)
     X3_LSTORE(0)
     __syncthreads();
-#if X3_MFMA16
     // (80-byte rows: the 16 rows of a 16-lane ds_read_b128 group start 5 r mod 16 sixteen-byte slots apart — all distinct)
     const int arow = (wm * 64 + l16) * X3_LD + kq * 8;
     const int brow = (wn * 64 + l16) * X3_LD + kq * 8;
-#else
-    const int arow = (wm * 64 + l32) * X3_LD + h * 8;
-    const int brow = (wn * 64 + l32) * X3_LD + h * 8;
-#endif
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) { X3_GLOAD((kt + 1) * g.kstep) }
         const _Float16* base = lds + cur * 4 * X3_TILE;
-#if X3_MFMA16
         {
             h16x8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
@@ -142,31 +121,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) X3_MMA16(acc[i], 0, 4, ah[i], al[i], bh, bl)
         }
-#else
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            h16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                ah[i] = *(const h16x8*)(base + 0 * X3_TILE + arow + i * 32 * X3_LD + ks * 16);
-                al[i] = *(const h16x8*)(base + 1 * X3_TILE + arow + i * 32 * X3_LD + ks * 16);
-                bh[i] = *(const h16x8*)(base + 2 * X3_TILE + brow + i * 32 * X3_LD + ks * 16);
-                bl[i] = *(const h16x8*)(base + 3 * X3_TILE + brow + i * 32 * X3_LD + ks * 16);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                    if constexpr (SINGLE) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bl[j], acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    }
-                }
-        }
-#endif
         if (kt + 1 < nk) X3_LSTORE(cur ^ 1)
         __syncthreads();
     }
@@ -175,17 +129,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
         // epilogue through LDS (see v2): 16-byte row-wise accesses instead of 64 scalar ones per lane
         constexpr int ELD = 68;
         float* park = (float*)lds + wave * (64 * ELD);
-#if X3_MFMA16
         x3_park16<4>(park, &acc[0][0], lane);
-#else
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[i][j][r];
-#endif
         __syncthreads();
         const int c4 = (lane & 15) * 4, rsub = lane >> 4;
         const int col = n0 + wn * 64 + c4;
@@ -230,29 +174,17 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f16x3_kernel(GemmX3Args g) {
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
-#if X3_MFMA16
     constexpr int NTI = 4, NTJ = 4, NR = 4;
-#else
-    constexpr int NTI = 2, NTJ = 2, NR = 16;
-#endif
 #pragma unroll
     for (int i = 0; i < NTI; ++i)
 #pragma unroll
         for (int j = 0; j < NTJ; ++j) {
-#if X3_MFMA16
             const int col = n0 + wn * 64 + j * 16 + l16;
-#else
-            const int col = n0 + wn * 64 + j * 32 + l32;
-#endif
             if (col >= g.N) continue;
             const float bv = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
-#if X3_MFMA16
                 const int row = m0 + wm * 64 + i * 16 + 4 * kq + r;
-#else
-                const int row = m0 + wm * 64 + i * 32 + mfma32_row(r, h);
-#endif
                 if (row >= g.M) continue;
                 float v = x3_alpha(g) * acc[i][j][r] + bv;
                 if (g.epilogue == RLCF_EPI_QUICKGELU) v = quick_gelu_fast(v);
@@ -311,25 +243,14 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     const int gsize = min(tiles_m - first_m, V2_GROUP_M), in_g = bid - grp * per_group;
     const int m0 = (first_m + in_g % gsize) * BM, n0 = (in_g / gsize) * V2_BN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
 
-#if X3_MFMA16
     const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 16-byte k chunk of this lane
-    (void)l32; (void)h; (void)kq;
     f32x4 acc[2 * RT][4];                           // 16-row tiles x 16-column tiles of the wave's (32 RT) x 64
 #pragma unroll
     for (int i = 0; i < 2 * RT; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-    f32x16 acc[RT][2];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
 
     // DMA sources: A tile = BM x 4 chunks (RT wave-instructions per wave per array), W tile = 512 (WPW each)
     const int qa0 = (wave * RT) * 64 + lane, qa1 = qa0 + 64, qw = (wave * WPW) * 64 + lane, qw1 = qw + 64;
@@ -358,46 +279,10 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         V2_PIECE(0, k0, sbi_) V2_PIECE(1, k0, sbi_) V2_PIECE(2, k0, sbi_) V2_PIECE(3, k0, sbi_) V2_PIECE(4, k0, sbi_) V2_PIECE(5, k0, sbi_) \
         V2_PIECE(6, k0, sbi_) V2_PIECE(7, k0, sbi_)                                                                      \
     }
-#define V2_LDFRAG(ks, AH, AL, BH, BL)                                                                                    \
-    {                                                                                                                    \
-        const int co_ = (((ks) * 2 + h) ^ swz) * 16;                                                                     \
-        _Pragma("unroll") for (int i = 0; i < RT; ++i) {                                                                 \
-            AH[i] = *(const h16x8*)(sb + aoff + i * 2048 + co_);                                                         \
-            AL[i] = *(const h16x8*)(sb + ALO + aoff + i * 2048 + co_);                                                   \
-        }                                                                                                                \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                  \
-            BH[i] = *(const h16x8*)(sb + WHI + boff + i * 2048 + co_);                                                   \
-            BL[i] = *(const h16x8*)(sb + WLO + boff + i * 2048 + co_);                                                   \
-        }                                                                                                                \
-    }
 // WLO0 (constexpr in scope; round 5): the weight's lo halves are all ZERO — the weight sits on the f16 grid, as every Linear / conv / projection
 // weight of a released CLIP checkpoint does (the archives store them as fp16; TPT/clip/model.py:399-436 copies them into float32
 // parameters) — so the product a_hi . w_lo adds exact zeros and its MFMA is dropped: two passes instead of three, the same bits
 // (up to the sign of an exact zero).  The engine finds out per weight at finalize (engine.hip make_split).
-#define V2_MMA3(i, j, AH, AL, BH, BL)                                                                                    \
-    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BH[j], acc[i][j], 0, 0, 0);                                \
-    if constexpr (SINGLE) {                                                                                              \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BL[j], acc[i][j], 0, 0, 0);                            \
-    } else {                                                                                                             \
-        if constexpr (!WLO0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BL[j], acc[i][j], 0, 0, 0);       \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BH[j], acc[i][j], 0, 0, 0);                            \
-    }
-// the same for the tile pair (i, 0), (i, 1), pass by pass: no MFMA directly follows its predecessor on the same accumulator (each
-// accumulator still takes its three products in the same order: bit-identical results; measured -0.9 % on the layer's four products)
-#define V2_MMA3_PAIR(i, AH, AL, BH, BL)                                                                                  \
-    acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BH[0], acc[i][0], 0, 0, 0);                                \
-    acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BH[1], acc[i][1], 0, 0, 0);                                \
-    if constexpr (SINGLE) {                                                                                              \
-        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BL[0], acc[i][0], 0, 0, 0);                            \
-        acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BL[1], acc[i][1], 0, 0, 0);                            \
-    } else {                                                                                                             \
-        if constexpr (!WLO0) {                                                                                           \
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BL[0], acc[i][0], 0, 0, 0);                        \
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BL[1], acc[i][1], 0, 0, 0);                        \
-        }                                                                                                                \
-        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BH[0], acc[i][0], 0, 0, 0);                            \
-        acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BH[1], acc[i][1], 0, 0, 0);                            \
-    }
 #define V2_FENCE __builtin_amdgcn_sched_barrier(0);
 // 16x16x32 fragments of the 64-byte-row image: lane l reads chunk l >> 4 (k = 8 (l >> 4) ..) of row base + (l & 15), slot chunk ^ ((r >> 2) & 3).
 // Bank map of a 16-lane ds_read_b128 group (16 consecutive rows, one chunk): row r starts at bank 16 (r & 3), its slot adds
@@ -424,13 +309,8 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     const int kb = kt0 * g.kstep;
     V2_ISSUE(kb, 0)
     if (nk > 1) V2_ISSUE(kb + g.kstep, 1)
-#if X3_MFMA16
     const int aoff = (wm * (32 * RT) + l16) * 64, boff = (wn * 64 + l16) * 64;      // row byte offsets
     const int co16 = (kq ^ ((l16 >> 2) & 3)) * 16;
-#else
-    const int swz = (l32 >> 2) & 3;
-    const int aoff = (wm * (32 * RT) + l32) * 64, boff = (wn * 64 + l32) * 64;      // row byte offsets
-#endif
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP) : "memory");      // the NP pieces of the newest stage may stay in flight
@@ -441,7 +321,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         const int kn = kb + (kt + 2) * g.kstep;
         char* sn = smem + (cur >= 1 ? cur - 1 : 2) * STAGE;                // stage (cur + 2) % 3
         const char* sb = smem + cur * STAGE;
-#if X3_MFMA16
         // 2 RT row tiles x two halves (column tiles 0-1 / 2-3) = the same number of MFMA groups of the same length as the 32x32x16 form
         // (6 MFMAs of k = 32 for 3 of twice the size), the DMA pieces between the same groups.  Only what the first group needs (6 fragments)
         // is read before it: nothing hides the LDS latency after the barrier on the small grids these forms serve
@@ -479,42 +358,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
             X3_MMA16(acc[1], 2, 2, ah[1], al[1], bh, bl)
             if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
         }
-#else
-        h16x8 ah0[RT], al0[RT], bh0[2], bl0[2], ah1[RT], al1[RT], bh1[2], bl1[2];
-        V2_LDFRAG(0, ah0, al0, bh0, bl0)
-        V2_FENCE
-        V2_MMA3(0, 0, ah0, al0, bh0, bl0) V2_FENCE
-        if (pf) V2_PIECE(0, kn, sn)
-        V2_LDFRAG(1, ah1, al1, bh1, bl1)
-        V2_FENCE
-        V2_MMA3(0, 1, ah0, al0, bh0, bl0) V2_FENCE
-        if constexpr (RT == 2) {
-            if (pf) V2_PIECE(1, kn, sn)
-            V2_FENCE
-            V2_MMA3(1, 0, ah0, al0, bh0, bl0) V2_FENCE
-            if (pf) V2_PIECE(2, kn, sn)
-            V2_FENCE
-            V2_MMA3(1, 1, ah0, al0, bh0, bl0) V2_FENCE
-            if (pf) V2_PIECE(3, kn, sn)
-            V2_FENCE
-            V2_MMA3(0, 0, ah1, al1, bh1, bl1) V2_FENCE
-            if (pf) { V2_PIECE(4, kn, sn) V2_PIECE(6, kn, sn) }
-            V2_FENCE
-            V2_MMA3(0, 1, ah1, al1, bh1, bl1) V2_FENCE
-            if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
-            V2_FENCE
-            V2_MMA3(1, 0, ah1, al1, bh1, bl1)
-            V2_MMA3(1, 1, ah1, al1, bh1, bl1)
-        } else {                            // one row tile per wave: four MFMA groups, the four pieces (A hi, A lo, W hi, W lo) between them
-            if (pf) V2_PIECE(2, kn, sn)
-            V2_FENCE
-            V2_MMA3(0, 0, ah1, al1, bh1, bl1) V2_FENCE
-            if (pf) { V2_PIECE(4, kn, sn) V2_PIECE(6, kn, sn) }
-            V2_FENCE
-            V2_MMA3(0, 1, ah1, al1, bh1, bl1)
-            if (pf) { V2_PIECE(5, kn, sn) V2_PIECE(7, kn, sn) }
-        }
-#endif
         cur = cur == 2 ? 0 : cur + 1;
     }
 
@@ -522,36 +365,18 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
     // re-reads it row-wise, so bias / residual / stores are 16-byte accesses covering whole 256-B row segments
     __syncthreads();
     if (const int ek = x3_epilogue_kind(g)) {
-#if X3_MFMA16
         if constexpr (RT == 2) {
             X3_EPILOGUE_SLAB(ek, g, &acc[0][0], (float*)smem + wave * (64 * 68), m0 + wm * 64, n0 + wn * 64, lane, am)
         } else {
             X3_EPILOGUE_HALFSLAB(ek, g, &acc[0][0], (float*)smem + wave * (32 * 68), m0 + wm * 32, n0 + wn * 64, lane, am)
         }
-#else
-        if constexpr (RT == 2) {
-            X3_EPILOGUE_SLAB(ek, g, acc[0][0], acc[0][1], acc[1][0], acc[1][1], (float*)smem + wave * (64 * 68), m0 + wm * 64, n0 + wn * 64, lane, am)
-        } else {
-            X3_EPILOGUE_HALFSLAB(ek, g, acc[0][0], acc[0][1], acc[0][0], acc[0][1], (float*)smem + wave * (32 * 68), m0 + wm * 32, n0 + wn * 64, lane, am)
-        }
-#endif
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
     {
         constexpr int ELD = 68;                                            // floats per parked row (64 + 4 pad)
         float* park = (float*)smem + wave * (32 * RT * ELD);
-#if X3_MFMA16
         x3_park16<2 * RT>(park, &acc[0][0], lane);
-#else
-#pragma unroll
-        for (int i = 0; i < RT; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[i][j][r];
-#endif
         __syncthreads();
         const int c4 = (lane & 15) * 4, rsub = lane >> 4;
         const int col = n0 + wn * 64 + c4;
@@ -618,7 +443,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
 #define V3_ALO 16384
 #define V3_WHI 32768
 #define V3_WLO 49152
-#if X3_MFMA16
 // The ping-pong K loop of the 256-row-class kernels (v3, v3i) in the 16x16x32 shape.  With k = 32 per instruction there is no k-substep to
 // split an iteration by, so the wave's tile is split by ROW tiles: first half = 16-row tiles 0 .. MT-1, second half = MT .. 2 MT - 1, the
 // W fragments stay live across both.  The two wave groups (wm = 0 / 1: the two waves of a SIMD) run half an iteration apart; two
@@ -678,7 +502,6 @@ __global__ __launch_bounds__(128 * NWM, NWM == 4 ? 2 : 1) void gemm_nt_f16x3_v2_
         __builtin_amdgcn_sched_barrier(0);                                                                               \
         _Pragma("unroll") for (int i = 0; i < MT; ++i) { X3_MMA16(acc[MT + i], 0, 4, ah[MT + i], al[MT + i], bh, bl) V2_FENCE } \
     }
-#endif
 __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) {
     constexpr bool SINGLE = false;      // (separate hi / lo arrays: the plain C-ABI call, split-f16 only)
     constexpr bool WLO0 = false;
@@ -695,26 +518,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
     const int gsize = min(tiles_m - first_m, 8), in_g = bid - grp * per_group;
     const int m0 = (first_m + in_g % gsize) * V3_BM, n0 = (in_g / gsize) * V3_BN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 2, wn = wave & 3, l32 = lane & 31, h = lane >> 5;
+    const int wm = wave >> 2, wn = wave & 3;
 
-#if X3_MFMA16
     constexpr int MT = 4;
     const int l16 = lane & 15, kq = lane >> 4;
-    (void)l32; (void)h;
     f32x4 acc[8][4];                                // 16-row tiles x 16-column tiles of the wave's 128 x 64
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
 
     // DMA: every operand tile = 256 rows x 4 chunks = 1024 chunks = 2 pieces per wave; 8 pieces per wave per stage
     size_t sa[2], sw[2];
@@ -731,29 +543,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
         else if ((idx) < 6) __builtin_amdgcn_global_load_lds((gptr_t)(g.Whi + sw[(idx) & 1] + (kk)), (lptr_t)((sb_) + V3_WHI + (wave * 2 + ((idx) & 1)) * 1024), 16, 0, 0);     \
         else __builtin_amdgcn_global_load_lds((gptr_t)(g.Wlo + sw[(idx) & 1] + (kk)), (lptr_t)((sb_) + V3_WLO + (wave * 2 + ((idx) & 1)) * 1024), 16, 0, 0);                    \
     }
-#define V3_LDA(ks, AH, AL)                                                                                               \
-    {                                                                                                                    \
-        const int co_ = (((ks) * 2 + h) ^ swz) * 16;                                                                     \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                  \
-            AH[i] = *(const h16x8*)(sb + aoff + i * 2048 + co_);                                                         \
-            AL[i] = *(const h16x8*)(sb + V3_ALO + aoff + i * 2048 + co_);                                                \
-        }                                                                                                                \
-    }
-#define V3_LDB(ks, BH, BL)                                                                                               \
-    {                                                                                                                    \
-        const int co_ = (((ks) * 2 + h) ^ swz) * 16;                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                  \
-            BH[j] = *(const h16x8*)(sb + V3_WHI + boff + j * 2048 + co_);                                                \
-            BL[j] = *(const h16x8*)(sb + V3_WLO + boff + j * 2048 + co_);                                                \
-        }                                                                                                                \
-    }
     const int nk = g.K / X3_BK;
     {
         char* s0 = smem;
 #pragma unroll
         for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, 0, s0)
     }
-#if X3_MFMA16
     const int aoff = (wm * 128 + l16) * 64, boff = (wn * 64 + l16) * 64;
     const int co16 = (kq ^ ((l16 >> 2) & 3)) * 16;          // (the 64-byte-row image of v2: see V2_LDA16)
 #define V3_LDA16(t0, n)                                                                                                  \
@@ -775,75 +570,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #undef V3_LDA16
 #undef V3_LDB16
 #undef V3_KT_PROLOGUE
-#else
-    const int swz = (l32 >> 2) & 3;
-    const int aoff = (wm * 128 + l32) * 64, boff = (wn * 64 + l32) * 64;
-    // Ping-pong: the two waves of a SIMD belong to the row groups wm = 0 / 1, which run the same K loop half an iteration apart.
-    // Two barriers per K tile (g = 2kt: tile kt has landed; g = 2kt+1); in every interval one group is in its pure-MFMA half
-    // (second k-substep, fragments already in registers) while the other waits for its first fragments, so the matrix pipe always
-    // has work.  Both groups issue their DMA pieces of tile kt+1 in the interval [2kt, 2kt+1].
-    h16x8 ah0[4], al0[4], bh0[2], bl0[2], ah1[4], al1[4], bh1[2], bl1[2];
-    if (wm == 0) {
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            const bool pf = kt + 1 < nk;
-            const int kn = (kt + 1) * g.kstep;
-            char* sn = smem + ((kt + 1) & 1) * V3_STAGE;
-            const char* sb = smem + (kt & 1) * V3_STAGE;
-            V3_LDA(0, ah0, al0) V3_LDB(0, bh0, bl0)
-            V2_FENCE
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                V2_MMA3_PAIR(i, ah0, al0, bh0, bl0) V2_FENCE
-                if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }
-                if (i == 0) { V3_LDA(1, ah1, al1) V3_LDB(1, bh1, bl1) }
-                V2_FENCE
-            }
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
-        }
-        __builtin_amdgcn_s_barrier();                              // pairs with the other group's last half step
-    } else {
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            const bool pf = kt + 1 < nk;
-            const int kn = (kt + 1) * g.kstep;
-            char* sn = smem + ((kt + 1) & 1) * V3_STAGE;
-            const char* sb = smem + (kt & 1) * V3_STAGE;
-            if (kt > 0) {                                          // second k-substep of tile kt-1 + the DMA of tile kt+1
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE
-                    if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }
-                    V2_FENCE
-                }
-            } else if (pf) {
-#pragma unroll
-                for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, kn, sn)
-            }
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            V3_LDA(0, ah0, al0) V3_LDB(0, bh0, bl0)
-            V2_FENCE
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                V2_MMA3_PAIR(i, ah0, al0, bh0, bl0) V2_FENCE
-                if (i == 0) { V3_LDA(1, ah1, al1) V3_LDB(1, bh1, bl1) }
-                V2_FENCE
-            }
-        }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
-    }
-#endif
     // epilogue through LDS, two passes of 64 rows per wave (8 waves x 64 x 68 floats = 139 KB)
     constexpr int ELD = 68;
     float* park = (float*)smem + wave * (64 * ELD);
@@ -855,16 +581,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
-#if X3_MFMA16
         x3_park16<4>(park, &acc[half * 4][0], lane);
-#else
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[half * 2 + i][j][r];
-#endif
         __syncthreads();
         if (col < g.N) {
             const float osd_ = g.Chi ? x3_out_scale(g) : 1.0f;   // scale of the split output, read BEFORE the first store of the loop (exactly 1 when none: v * 1 == v)
@@ -912,84 +629,27 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3_kernel(GemmX3Args g) 
 #ifndef V3_AUX_W
 #define V3_AUX_W 0
 #endif
-// Stream-K tail (template flag SK; launch_gemm_f16x3).  With one 139-KB workgroup per CU a launch of T tiles costs ceil(T / 256) tile
-// rounds, however few tiles the last round holds (out_proj at 20 images per pass: 2955 tiles = 11.54 rounds -> 12; one image: 150
-// tiles on 256 CUs; the reward tower of a pass: 279 tiles).  The first sk_first = 256 * floor(T / 256) tiles stay whole-tile workgroups
-// (the plain instantiation, launched first); the K steps of the remaining R tiles are shared out evenly by a second launch:
-//   * the R tiles are cut into 8 chunks of whole tiles, chunk x served by the workgroups s with s % 8 == x (workgroups are dealt
-//     round-robin to the XCDs, so a chunk's workgroups share an L2 and no dependency crosses chunks);
-//   * inside a chunk the unit list (tile, k) is cut into q = sk_blocks / 8 contiguous ranges of <= nk units; a range touches at
-//     most two tiles and is worked on from its END: its FIRST piece is its part of the last tile it touches (workgroup s of the
-//     launch), its SECOND piece — if it straddles a tile boundary — the tail of the tile before (a workgroup of the second half of
-//     the grid, handed out shortest-first-piece first so that the two pieces of a range add up to the same time on whichever CU takes
-//     them: the CUs come free in the order of their first pieces);
-//   * the piece that ENDS a tile (k1 == nk) owns the tile: every other part of that tile is the first piece of a LOWER-numbered range
-//     of the chunk — a workgroup with a lower index (dispatched earlier, it never waits itself) — so the owner never waits for a
-//     workgroup that is not yet resident, and normally finds the parts already published;
-//   * a non-owner writes its raw accumulators to its slab with write-through (sc1) 16-byte stores in register layout (coalesced, no
-//     LDS pass), every wave drains vmcnt, one lane publishes the launch's epoch in the range's flag word (relaxed, agent scope); the
-//     owner polls that word relaxed, takes ONE agent-scope acquire, adds the slabs in increasing-k order with sc1 loads (fixed order:
-//     bit-reproducible) and runs the epilogue (cdna_hip_programming.md, Guideline 16 / R1).
 // MT = 32-row accumulator tiles per wave group: 4 = the 256-row tile; 3 = a 192-row tile for launches whose 256-row tiles fill
 // little more than half of one round of workgroups (one image's token matrix against a W x W / W x 4W weight: 150 tiles on 256 CUs
 // -> 198 tiles of 3/4 the work each)
-template <bool SINGLE, bool CONV = false, bool SK = false, int MT = 4, int WLO0 = 0>       // WLO0: 0 three passes, 1 two passes (w_lo == 0), 2 two passes + packed hi-only W
+template <bool SINGLE, bool CONV = false, int MT = 4, int WLO0 = 0>       // WLO0: 0 three passes, 1 two passes (w_lo == 0), 2 two passes + packed hi-only W
 __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g) {
-    static_assert(MT == 4 || (MT == 3 && !SK && !CONV), "192-row tiles: plain products only");
+    static_assert(MT == 4 || (MT == 3 && !CONV), "192-row tiles: plain products only");
     constexpr int BM = MT * 64;
     float am = 0.f;                 // max|C| of this thread's outputs (amax_out)
     extern __shared__ __attribute__((aligned(16))) char smem[];       // [2][V3_STAGE] (+ epilogue parking)
     const int tiles_n = (g.N + V3_BN - 1) / V3_BN, tiles_m = (g.M + BM - 1) / BM;
-    int bid, k0 = 0, k1 = g.K / X3_BK;
-    int sk_chunk = 0, sk_idx = 0, sk_q = 1, sk_units = 1, sk_tile_c = 0;
-    if constexpr (!SK) {
-        const int nwg = gridDim.x;
-        bid = blockIdx.x;
-        if (g.stagger > 1 && blockIdx.x < 256) {                        // (see GemmX3Args::stagger)
-            const int c = (blockIdx.x >> 3) % g.stagger;
-            const int cyc = c * (k1 * 5200 + 12000) / g.stagger;        // ~ cycles per tile: ~5 200 per K tile of 32 + epilogue
-            for (int q2 = cyc >> 13; q2 > 0; --q2) __builtin_amdgcn_s_sleep(127);       // (127 x 64 cycles ~ 2^13)
-        }
+    const int nk = g.K / X3_BK;
+    const int nwg = gridDim.x;
+    int bid = blockIdx.x;
+    if (g.stagger > 1 && blockIdx.x < 256) {                        // (see GemmX3Args::stagger)
+        const int c = (blockIdx.x >> 3) % g.stagger;
+        const int cyc = c * (nk * 5200 + 12000) / g.stagger;        // ~ cycles per tile: ~5 200 per K tile of 32 + epilogue
+        for (int q2 = cyc >> 13; q2 > 0; --q2) __builtin_amdgcn_s_sleep(127);       // (127 x 64 cycles ~ 2^13)
+    }
+    {
         const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    } else {
-        const int nk_full = g.K / X3_BK;
-        int s_ = blockIdx.x;
-        const bool second = s_ >= g.sk_blocks;                         // the second piece of some range of this chunk
-        if (second) s_ -= g.sk_blocks;
-        const int R = tiles_m * tiles_n - g.sk_first;
-        sk_chunk = s_ & 7; sk_idx = s_ >> 3; sk_q = g.sk_blocks >> 3;
-        const int c0 = sk_chunk * R / 8, c1 = (sk_chunk + 1) * R / 8;       // (32-bit throughout: R < 256, <= 32 tiles x nk units per chunk)
-        sk_units = (c1 - c0) * nk_full;
-        if (sk_units <= 0) return;
-        if (second) {
-            // rank this chunk's two-piece ranges by (length of the first piece, index); this workgroup takes the one of rank sk_idx
-            int* pick = (int*)smem;
-            if (threadIdx.x == 0) *pick = -1;
-            __syncthreads();
-            if ((int)threadIdx.x < sk_q) {
-                auto key = [&](int i) -> int {
-                    const int a_ = i * sk_units / sk_q, b_ = (i + 1) * sk_units / sk_q;
-                    if (b_ <= a_ || a_ / nk_full == (b_ - 1) / nk_full) return 0x7fffffff;               // empty, or one piece only
-                    return (b_ - ((b_ - 1) / nk_full) * nk_full) * 64 + i;
-                };
-                const int mine = key(threadIdx.x);
-                int rank = 0;
-                for (int i = 0; i < sk_q; ++i) rank += key(i) < mine ? 1 : 0;
-                if (mine != 0x7fffffff && rank == sk_idx) *pick = threadIdx.x;
-            }
-            __syncthreads();
-            sk_idx = __builtin_amdgcn_readfirstlane(*pick);                // (wave-uniform: everything derived from it stays scalar)
-            __syncthreads();
-            if (sk_idx < 0) return;                                         // (fewer two-piece ranges than workgroups)
-        }
-        const int ua = sk_idx * sk_units / sk_q, ub = (sk_idx + 1) * sk_units / sk_q;
-        if (ub <= ua) return;                                               // (more workgroups than units in this chunk)
-        const int tb = (ub - 1) / nk_full, ta = ua / nk_full;
-        if (second && ta == tb) return;
-        if (!second) { sk_tile_c = tb; k0 = max(ua, tb * nk_full) - tb * nk_full; k1 = ub - tb * nk_full; }
-        else { sk_tile_c = ta; k0 = ua - ta * nk_full; k1 = nk_full; }
-        bid = g.sk_first + c0 + sk_tile_c;
     }
     // M tiles per scheduling group: 8 (16 / 32: -1.5 / -8 %, measured); RLCF_X3_GROUP pins it (measurements)
     const int G = g.tile_group % 100 > 0 ? g.tile_group % 100 : 8;
@@ -1001,25 +661,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
     const int m0 = (nfast ? first_m + in_g / tiles_n : first_m + in_g % gsize) * BM;
     const int n0 = (nfast ? in_g % tiles_n : in_g / gsize) * V3_BN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 2, wn = wave & 3, l32 = lane & 31, h = lane >> 5;
+    const int wm = wave >> 2, wn = wave & 3;
 
-#if X3_MFMA16
     const int l16 = lane & 15, kq = lane >> 4;      // fragment row (column) and 16-byte k chunk of this lane
-    (void)l32; (void)h;
     f32x4 acc[2 * MT][4];                           // 16-row tiles x 16-column tiles of the wave's (32 MT) x 64
 #pragma unroll
     for (int i = 0; i < 2 * MT; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#endif
 
     // DMA: every operand tile = 256 rows x 4 chunks = 1024 chunks = 2 pieces per wave; 8 pieces per wave per stage
     // Interleaved operands: row r of A (and W) holds, per K tile, one 128-byte block [32 hi | 32 lo]; a DMA instruction moves 8 rows
@@ -1035,8 +684,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
         // (MT = 3: the A tile is 192 rows = 3 pieces per wave, piece j of wave w = rows 8 (3 w + j) ..)
         const int qa = (wave * MT + j) * 64 + lane, ra = MT == 4 ? r : qa >> 3, ca = MT == 4 ? c : ((qa & 7) ^ ((ra >> 1) & 7)) * 8;
         const int row = min(m0 + ra, g.M - 1);
-        sa[j] = (size_t)row * g.lda + ca + (SK ? (size_t)k0 * g.kstep : (size_t)0);        // (stream-K pieces start at K step k0)
-        sw[j] = (size_t)min(n0 + r, g.N - 1) * g.ldw + c + (SK ? (size_t)k0 * g.kstep : (size_t)0);
+        sa[j] = (size_t)row * g.lda + ca;
+        sw[j] = (size_t)min(n0 + r, g.N - 1) * g.ldw + c;
         if constexpr (WLO0 == 2) swp[j] = (size_t)min(n0 + r, g.N - 1) * g.ldwpk + c;
         if constexpr (CONV) {
             const int ox = row % g.conv_W, oy = (row / g.conv_W) % g.conv_H;
@@ -1071,32 +720,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
             if (wnext_) __builtin_amdgcn_global_load_lds((gptr_t)(g.Wpk + swp[(idx) & 3] + kkw_), (lptr_t)(smem + wb_ * V3_STAGE + 32768 + (wave * 4 + ((idx) & 3)) * 1024), 16, 0, V3_AUX_W); \
         } else __builtin_amdgcn_global_load_lds((gptr_t)(g.Whi + sw[(idx) & 3] + (kk)), (lptr_t)((sb_) + 32768 + (wave * 4 + ((idx) & 3)) * 1024), 16, 0, V3_AUX_W);              \
     }
-#undef V3_LDA
-#undef V3_LDB
-#define V3_LDA(ks, AH, AL)                                                                                               \
-    {                                                                                                                    \
-        const int ch_ = (((ks) * 2 + h) ^ swz) * 16, cl_ = ((4 + (ks) * 2 + h) ^ swz) * 16;                              \
-        _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                 \
-            AH[i] = *(const h16x8*)(sb + aoff + i * 4096 + ch_);                                                         \
-            AL[i] = *(const h16x8*)(sb + aoff + i * 4096 + cl_);                                                         \
-        }                                                                                                                \
-    }
-#define V3_LDB(ks, BH, BL)                                                                                               \
-    {                                                                                                                    \
-        if constexpr (WLO0 == 2) {                                                                                       \
-            /* K tile kt = half (kt & 1) of its pair's 128-byte rows (chunks 0-3 / 4-7), in the W buffer of the pair's parity */ \
-            const int ch_ = ((((kt) & 1) * 4 + (ks) * 2 + h) ^ swz) * 16;                                                  \
-            const char* sw_ = smem + (((kt) >> 1) & 1) * V3_STAGE + 32768 + boff;                                          \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) { BH[j] = *(const h16x8*)(sw_ + j * 4096 + ch_); BL[j] = BH[j]; }  \
-        } else {                                                                                                         \
-        const int ch_ = (((ks) * 2 + h) ^ swz) * 16, cl_ = ((4 + (ks) * 2 + h) ^ swz) * 16;                              \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                  \
-            BH[j] = *(const h16x8*)(sb + 32768 + boff + j * 4096 + ch_);                                                 \
-            BL[j] = *(const h16x8*)(sb + 32768 + boff + j * 4096 + cl_);                                                 \
-        }                                                                                                                \
-        }                                                                                                                \
-    }
-    const int nk = SK ? k1 - k0 : g.K / X3_BK;
     int ctap_ = 0;
     long coff_ = 0;
     if constexpr (CONV) coff_ = conv_off(0, ctap_);
@@ -1107,7 +730,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
         for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, 0, s0)
     }
-#if X3_MFMA16
     // 16x16x32 fragments: lane l reads hi chunk l >> 4, or lo chunk 4 + (l >> 4), of row base + (l & 15) (base a multiple of 16, so the
     // row's swizzle is (l & 15) >> 1): a 16-lane ds_read_b128 group reads 16 consecutive rows of one chunk — the case the slot
     // swizzle above makes conflict-free.  2 MT A row tiles x (hi, lo) + 4 W column tiles x (hi, lo) reads per wave and K tile.
@@ -1145,155 +767,16 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #undef V3_LDA16
 #undef V3_LDB16
 #undef V3_KT_PROLOGUE
-#else
-    const int swz = (l32 >> 1) & 7;
-    const int aoff = (wm * (MT * 32) + l32) * 128, boff = (wn * 64 + l32) * 128;
-    // Ping-pong: the two waves of a SIMD belong to the row groups wm = 0 / 1, which run the same K loop half an iteration apart.
-    // Two barriers per K tile (g = 2kt: tile kt has landed; g = 2kt+1); in every interval one group is in its pure-MFMA half
-    // (second k-substep, fragments already in registers) while the other waits for its first fragments, so the matrix pipe always
-    // has work.  Both groups issue their DMA pieces of tile kt+1 in the interval [2kt, 2kt+1].
-    h16x8 ah0[MT], al0[MT], bh0[2], bl0[2], ah1[MT], al1[MT], bh1[2], bl1[2];
-    if (wm == 0) {
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            const bool pf = kt + 1 < nk;
-            const int kn = (kt + 1) * g.kstep;
-            const bool wnext_ = ((kt + 1) & 1) == 0; const int kkw_ = ((kt + 1) >> 1) * 64, wb_ = ((kt + 1) >> 1) & 1;      // (WLO0 == 2)
-            (void)wnext_; (void)kkw_; (void)wb_;
-            if constexpr (CONV) { if (pf) coff_ = conv_off(kt + 1, ctap_); }
-            char* sn = smem + ((kt + 1) & 1) * V3_STAGE;
-            const char* sb = smem + (kt & 1) * V3_STAGE;
-            V3_LDA(0, ah0, al0) V3_LDB(0, bh0, bl0)
-            V2_FENCE
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                V2_MMA3_PAIR(i, ah0, al0, bh0, bl0) V2_FENCE
-                if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }
-                if (MT == 3 && i == 2 && pf) { V3_PIECE(6, kn, sn) V3_PIECE(7, kn, sn) }
-                if (i == 0) { V3_LDA(1, ah1, al1) V3_LDB(1, bh1, bl1) }
-                V2_FENCE
-            }
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
-        }
-        __builtin_amdgcn_s_barrier();                              // pairs with the other group's last half step
-    } else {
-        for (int kt = 0; kt < nk; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            const bool pf = kt + 1 < nk;
-            const int kn = (kt + 1) * g.kstep;
-            const bool wnext_ = ((kt + 1) & 1) == 0; const int kkw_ = ((kt + 1) >> 1) * 64, wb_ = ((kt + 1) >> 1) & 1;      // (WLO0 == 2)
-            (void)wnext_; (void)kkw_; (void)wb_;
-            if constexpr (CONV) { if (pf) coff_ = conv_off(kt + 1, ctap_); }
-            char* sn = smem + ((kt + 1) & 1) * V3_STAGE;
-            const char* sb = smem + (kt & 1) * V3_STAGE;
-            if (kt > 0) {                                          // second k-substep of tile kt-1 + the DMA of tile kt+1
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE
-                    if (pf) { V3_PIECE(i * 2, kn, sn) V3_PIECE(i * 2 + 1, kn, sn) }
-                    if (MT == 3 && i == 2 && pf) { V3_PIECE(6, kn, sn) V3_PIECE(7, kn, sn) }
-                    V2_FENCE
-                }
-            } else if (pf) {
-#pragma unroll
-                for (int pi = 0; pi < 8; ++pi) V3_PIECE(pi, kn, sn)
-            }
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            V3_LDA(0, ah0, al0) V3_LDB(0, bh0, bl0)
-            V2_FENCE
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                V2_MMA3_PAIR(i, ah0, al0, bh0, bl0) V2_FENCE
-                if (i == 0) { V3_LDA(1, ah1, al1) V3_LDB(1, bh1, bl1) }
-                V2_FENCE
-            }
-        }
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) { V2_MMA3_PAIR(i, ah1, al1, bh1, bl1) V2_FENCE }
-    }
-#endif
-    if constexpr (SK) {
-        const int nk_full = g.K / X3_BK;
-        if (k1 < nk_full) {
-            // ---- a part that does not end its tile: publish the raw accumulators (register layout: 32 x 16 B per thread, coalesced)
-            const int gid = sk_chunk + 8 * sk_idx;                      // this range's slab / flag
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((char*)g.sk_ws + (size_t)gid * X3_SK_SLAB_BYTES, 0, X3_SK_SLAB_BYTES, 0x00020000);
-#pragma unroll
-            for (int q = 0; q < 32; ++q) {
-#if X3_MFMA16
-                const f32x4 v_ = acc[q >> 2][q & 3];                    // (register layout of THIS build: written and read by the same kernel)
-#else
-                const f32x16& a_ = acc[q >> 3][(q >> 2) & 1];
-                const f32x4 v_ = {a_[(q & 3) * 4], a_[(q & 3) * 4 + 1], a_[(q & 3) * 4 + 2], a_[(q & 3) * 4 + 3]};
-#endif
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v_), rs, (q * 512 + t) * 16, 0, 16 /* sc1: write-through */);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // EVERY storing wave drains its stores ...
-            __syncthreads();
-            if (t == 0) __hip_atomic_store(g.sk_flags + gid, g.sk_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... then ONE lane publishes
-            return;
-        }
-        // ---- the part that ends the tile: add the earlier parts (ranges first .. sk_idx - 1 of this chunk) in increasing-k order
-        const int first = ((sk_tile_c * nk_full + 1) * sk_q - 1) / sk_units;                      // range holding the tile's K step 0
-        for (int pi = first; pi < sk_idx; ++pi) {
-            const int gp = sk_chunk + 8 * pi;
-            if (t == 0) {
-                unsigned spins = 0;
-                while (__hip_atomic_load(g.sk_flags + gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g.sk_epoch) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > (1u << 22)) { __hip_atomic_store(g.sk_flags + X3_SK_MAX_BLOCKS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            __syncthreads();
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((char*)g.sk_ws + (size_t)gp * X3_SK_SLAB_BYTES, 0, X3_SK_SLAB_BYTES, 0x00020000);
-#pragma unroll
-            for (int q8 = 0; q8 < 4; ++q8) {
-                u32x4 v_[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v_[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((q8 * 8 + u) * 512 + t) * 16, 0, 16 /* sc1 */);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int q = q8 * 8 + u;
-                    const f32x4 f_ = __builtin_bit_cast(f32x4, v_[u]);
-#if X3_MFMA16
-                    acc[q >> 2][q & 3] += f_;
-#else
-                    f32x16& a_ = acc[q >> 3][(q >> 2) & 1];
-                    a_[(q & 3) * 4] += f_[0]; a_[(q & 3) * 4 + 1] += f_[1]; a_[(q & 3) * 4 + 2] += f_[2]; a_[(q & 3) * 4 + 3] += f_[3];
-#endif
-                }
-            }
-        }
-    }
     if (const int ek = x3_epilogue_kind(g)) {
         float* parkf = (float*)smem + wave * (64 * 68);
         __syncthreads();
         // (written out, not a `#pragma unroll` loop over the halves: with every epilogue kind inlined the loop body exceeds the pragma-unroll
         //  size limit once the pair kinds carry the line-complete stores — the loop then stays a loop and acc[half * 2] becomes scratch)
-#if X3_MFMA16
         X3_EPILOGUE_SLAB(ek, g, &acc[0][0], parkf, m0 + wm * (MT * 32), n0 + wn * 64, lane, am)              // 16-row tiles 0-3
         if constexpr (MT == 4)
             X3_EPILOGUE_SLAB(ek, g, &acc[4][0], parkf, m0 + wm * (MT * 32) + 64, n0 + wn * 64, lane, am)
         if constexpr (MT == 3)           // 16-row tiles 4-5: half a slab
             X3_EPILOGUE_HALFSLAB(ek, g, &acc[4][0], parkf, m0 + wm * 96 + 64, n0 + wn * 64, lane, am)
-#else
-        X3_EPILOGUE_SLAB(ek, g, acc[0][0], acc[0][1], acc[1][0], acc[1][1], parkf, m0 + wm * (MT * 32), n0 + wn * 64, lane, am)
-        if constexpr (MT == 4)
-            X3_EPILOGUE_SLAB(ek, g, acc[2][0], acc[2][1], acc[3][0], acc[3][1], parkf, m0 + wm * (MT * 32) + 64, n0 + wn * 64, lane, am)
-        if constexpr (MT == 3)           // the third 32-row tile: half a slab
-            X3_EPILOGUE_HALFSLAB(ek, g, acc[2][0], acc[2][1], acc[2][0], acc[2][1], parkf, m0 + wm * 96 + 64, n0 + wn * 64, lane, am)
-#endif
         amax_commit(g.amax_out, am); x3_publish_scale(g);
         return;
     }
@@ -1308,18 +791,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_f16x3_v3i_kernel(GemmX3Args g)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
-#if X3_MFMA16
         if (half == 0) x3_park16<4>(park, &acc[0][0], lane);
         else x3_park16<2 * MT - 4>(park, &acc[4][0], lane);
-#else
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (half * 2 + i < MT) park[(i * 32 + mfma32_row(r, h)) * ELD + j * 32 + l32] = acc[half * 2 + i < MT ? half * 2 + i : 0][j][r];
-#endif
         __syncthreads();
         if (col < g.N) {
             const float osd_ = g.Chi ? x3_out_scale(g) : 1.0f;   // scale of the split output, read BEFORE the first store of the loop (exactly 1 when none: v * 1 == v)
@@ -1407,152 +880,6 @@ __global__ __launch_bounds__(256) void gemm_x3_splitk_reduce_kernel(GemmX3Args g
             if (g.Clo) *(h16x4*)(g.Clo + (size_t)row * g.ldch + x3_ocol(g, col)) = ll;
         }
     }
-    amax_commit(g.amax_out, am); x3_publish_scale(g);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------
-// 256x256 tile on FOUR waves (one per SIMD, 492 registers each: 256 accumulators in AGPRs), wave tile 128x128 = 4x4 MFMA tiles.
-// EXPERIMENTAL, off by default (RLCF_X3_V4=1; 2 / 3 = the no-DMA / no-MFMA ablations): per K tile a wave reads 32 fragments for 96
-// MFMAs where the 8-wave kernel reads 24 for 48 (a third less LDS -> register traffic per flop) and there is ONE barrier per K tile.
-// With a single wave per SIMD nothing else covers its latencies, so the wave pipelines itself: one memory instruction behind each
-// MFMA, the fragments of a k-substep read during the MFMAs of the previous one, the barrier in the MIDDLE of the second substep
-// (everyone has read the tile's slots by then) and the first fragments of tile kt+1 read behind the remaining MFMAs of tile kt.
-// Measured (profiles/r3_gemm_experiments.txt): the main loop runs at the SAME 2.45 us per K tile as the 8-wave kernel, the four-slab
-// epilogue of a wave costs the K = 768 shapes 4-9 %, and under sustained load both kernels sit on the 1400 W socket power limit
-// (8-wave: 1506 MHz, 386 TF; this one: 1575 MHz, 381 TF; without its DMA 1775 MHz, 458 TF): what bounds the product is energy per
-// flop, not a latency the schedule leaves exposed.  Interleaved operands (kstep 64), compile-time epilogues (x3_epilogue_kind != 0).
-template <int ABL>          // ABL (measurements only): 1 = no DMA after the prologue, 2 = no MFMAs
-__global__ __launch_bounds__(256, 1) void gemm_nt_f16x3_v4_kernel(GemmX3Args g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];       // [2][V3_STAGE]
-    const int tiles_n = (g.N + V3_BN - 1) / V3_BN, tiles_m = (g.M + V3_BM - 1) / V3_BM;
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int per_group = 8 * tiles_n, grp = bid / per_group, first_m = grp * 8;
-    const int gsize = min(tiles_m - first_m, 8), in_g = bid - grp * per_group;
-    const int m0 = (first_m + in_g % gsize) * V3_BM, n0 = (in_g / gsize) * V3_BN;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, h = lane >> 5;
-
-    f32x16 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // DMA: a stage = 256 A rows + 256 W rows x 128 B = 64 pieces of 8 rows; wave w moves A pieces 8w..8w+7 and W pieces 8w..8w+7
-    size_t sa[8], sw[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int q = (wave * 8 + j) * 64 + lane, r = q >> 3, c = ((q & 7) ^ ((r >> 1) & 7)) * 8;
-        sa[j] = (size_t)min(m0 + r, g.M - 1) * g.lda + c;
-        sw[j] = (size_t)min(n0 + r, g.N - 1) * g.ldw + c;
-    }
-    // LDS: A ring of THREE 32-KB slots at [0, 96 KB), W ring of two at [96 KB, 160 KB).  The A tiles are unique to the workgroup and
-    // come from HBM / the MALL, the W tiles are hot in every L2: A pieces go out two K tiles ahead, W pieces one -- a K tile's worth of
-    // operands (64 KB) in flight per CU does not cover the loaded memory latency at this request rate (64 KB per ~1.8 us).
-#define V4_WBASE 98304
-#define V4_PA(j, kk, slot) __builtin_amdgcn_global_load_lds((gptr_t)(g.Ahi + sa[j] + (kk)), (lptr_t)(smem + (slot) * 32768 + (wave * 8 + (j)) * 1024), 16, 0, 0);
-#define V4_PW(j, kk, slot) __builtin_amdgcn_global_load_lds((gptr_t)(g.Whi + sw[j] + (kk)), (lptr_t)(smem + V4_WBASE + (slot) * 32768 + (wave * 8 + (j)) * 1024), 16, 0, 0);
-    const int swz = (l32 >> 1) & 7;
-    const int aoff = (wm * 128 + l32) * 128, boff = V4_WBASE + (wn * 128 + l32) * 128;
-#define V4_M(n, i, AH, AL, BH, BL)                                                                                       \
-    if (ABL != 2) acc[i][(n) & 3] = __builtin_amdgcn_mfma_f32_32x32x16_f16((n) < 8 ? AH[i] : AL[i], ((n) >> 2) == 1 ? BL[(n) & 3] : BH[(n) & 3], acc[i][(n) & 3], 0, 0, 0);
-    // read q (0..3) of row tile i of a k-substep: A hi, A lo, W hi, W lo (sa_ / sw_: byte offsets of the A / W slots)
-#define V4_RD(ks, i, q, AH, AL, BH, BL, sa_, sw_)                                                                       \
-    {                                                                                                                    \
-        const int ch_ = (((ks) * 2 + h) ^ swz) * 16, cl_ = ((4 + (ks) * 2 + h) ^ swz) * 16;                              \
-        if ((q) == 0) AH[i] = *(const h16x8*)(smem + (sa_) + aoff + (i) * 4096 + ch_);                                   \
-        else if ((q) == 1) AL[i] = *(const h16x8*)(smem + (sa_) + aoff + (i) * 4096 + cl_);                              \
-        else if ((q) == 2) BH[i] = *(const h16x8*)(smem + (sw_) + boff + (i) * 4096 + ch_);                              \
-        else BL[i] = *(const h16x8*)(smem + (sw_) + boff + (i) * 4096 + cl_);                                            \
-    }
-    const int nk = g.K / X3_BK;
-    h16x8 ah0[4], al0[4], bh0[4], bl0[4], ah1[4], al1[4], bh1[4], bl1[4];
-    // prologue: A(0), W(0), then A(1), W(1)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) V4_PA(j, 0, 0)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) V4_PW(j, 0, 0)
-    if (nk > 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) V4_PA(j, g.kstep, 1)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) V4_PW(j, g.kstep, 1)
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) V4_RD(0, i, q, ah0, al0, bh0, bl0, 0, 0)
-    int as_cur = 0;                                       // A slot of tile kt (kt % 3)
-    for (int kt = 0; kt < nk; ++kt) {
-        const int as_nxt = as_cur == 2 ? 0 : as_cur + 1, as_nn = as_nxt == 2 ? 0 : as_nxt + 1;    // slots of tiles kt+1, kt+2
-        const int ao = as_cur * 32768, an = as_nxt * 32768, wo = (kt & 1) * 32768, wn_ = ((kt + 1) & 1) * 32768;
-        const bool pf1 = kt + 1 < nk, pf2 = kt + 2 < nk && ABL != 1;
-        const int k2 = (kt + 2) * g.kstep;
-        // substep 0: MFMAs on F0; behind them the fragments of substep 1 and the A pieces of tile kt+2
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int n = 0; n < 12; ++n) {
-                V4_M(n, i, ah0, al0, bh0, bl0) V2_FENCE
-                if (n < 4) V4_RD(1, i, n, ah1, al1, bh1, bl1, ao, wo)
-                if (pf2 && i < 2 && n >= 4 && (n & 1) == 0) V4_PA(i * 4 + ((n - 4) >> 1), k2, as_nn)
-                V2_FENCE
-            }
-        }
-        // substep 1, first half
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int n = 0; n < 12; ++n) V4_M(n, i, ah1, al1, bh1, bl1)
-            V2_FENCE
-        }
-        // every wave has read the slots of tile kt; A(kt+1) and W(kt+1) have landed (the 8 pieces of A(kt+2) may still be in flight)
-        if (pf2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // second half: behind the MFMAs the first fragments of tile kt+1 and the W pieces of tile kt+2 (into the W slot of tile kt)
-#pragma unroll
-        for (int i = 2; i < 4; ++i) {
-#pragma unroll
-            for (int n = 0; n < 12; ++n) {
-                V4_M(n, i, ah1, al1, bh1, bl1) V2_FENCE
-                if (pf1 && n < 8) V4_RD(0, (i - 2) * 2 + (n >> 2), n & 3, ah0, al0, bh0, bl0, an, wn_)
-                if (pf2 && n >= 8) V4_PW((i - 2) * 4 + (n - 8), k2, kt & 1)
-                V2_FENCE
-            }
-        }
-        as_cur = as_nxt;
-    }
-    const int ek = x3_epilogue_kind(g);
-    float* parkf = (float*)smem + wave * (64 * 68);
-    float am = 0.f;
-    __syncthreads();
-    // (kinds 1-4 in their LEAN form: with the ResNet additions of the epilogue -- device alpha, ReLU, max|C|, output scale -- the 492
-    // registers no longer suffice and the accumulators spill; the launcher sends those products to the 8-wave kernel)
-#define V4_SLAB(...)                                                                                                     \
-    {                                                                                                                    \
-        if (ek == 1) x3_epilogue_slab<RLCF_EPI_NONE, false, true, false, true>(__VA_ARGS__);                             \
-        else if (ek == 2) x3_epilogue_slab<RLCF_EPI_NONE, true, true, false, true>(__VA_ARGS__);                         \
-        else if (ek == 3) x3_epilogue_slab<RLCF_EPI_QUICKGELU, false, false, true, true>(__VA_ARGS__);                   \
-        else x3_epilogue_slab<RLCF_EPI_NONE, false, false, true, true>(__VA_ARGS__);                                     \
-    }
-#pragma unroll
-    for (int hr = 0; hr < 2; ++hr)
-#pragma unroll
-        for (int hc = 0; hc < 2; ++hc)
-            V4_SLAB(g, acc[hr * 2][hc * 2], acc[hr * 2][hc * 2 + 1], acc[hr * 2 + 1][hc * 2], acc[hr * 2 + 1][hc * 2 + 1], parkf,
-                    m0 + wm * 128 + hr * 64, n0 + wn * 128 + hc * 64, lane, am)
     amax_commit(g.amax_out, am); x3_publish_scale(g);
 }
 
@@ -1803,13 +1130,23 @@ static inline void x3_apply_next(GemmX3Args& g, const X3Next& n) {
     g.bnd_in = n.b.in; g.bnd_res = n.b.res; g.bnd_gain = n.b.gain; g.bnd_bmax = n.b.bmax; g.bnd_out2 = n.b.out2;
     g.col_scale = n.col_scale;
 }
-int g_last_x3_variant = 0;          // 1 = 128x128 register-staged kernel, 2 = 256x128 DMA-ring kernel (profiling tag)
+int g_last_x3_variant = 0;          // 1 = 128x128 register-staged kernel, 2 = 256x128 DMA-ring kernel (profiling tag; set before the launch is
+                                    // attempted, so it also names a kernel whose launch failed)
+// one launch of a kernel of the family: its dynamic-LDS limit (set once per kernel), the launch, the launch check
+template <class K>
+static int x3_launch(K kernel, dim3 grid, int threads, size_t lds, hipStream_t st, const GemmX3Args& g) {
+    const int rc = rlcf_func_lds((const void*)kernel, lds);
+    if (rc != RLCF_OK) return rc;
+    kernel<<<grid, dim3(threads), lds, st>>>(g);
+    RLCF_LAUNCH_CHECK();
+    return RLCF_OK;
+}
 // splitk_ws / splitk_ws_bytes: caller-owned scratch for the split-K form of the small-grid kernel (the engine sizes it once at
 // create); without it those shapes run unsplit.  Nothing is allocated here.
 int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi, const void* Wlo, int ldw, const float* bias,
                       const float* residual, int ldr, const float* aux, int ldaux, float* C, int ldc, void* Chi, void* Clo, int ldch,
                       int M, int N, int K, float alpha, int epilogue, hipStream_t st, const float* alpha_dev, unsigned int* amax_out, int c_il,
-                      float* splitk_ws, size_t splitk_ws_bytes, int single, const float* out_scale_dev, unsigned* sk_epoch) {
+                      float* splitk_ws, size_t splitk_ws_bytes, int single, const float* out_scale_dev) {
     const X3Next next = x3_take_next();
     RLCF_ARG_CHECK(M > 0 && N > 0 && K > 0 && K % X3_BK == 0 && lda % 8 == 0 && ldw % 8 == 0);
     const bool wlo0 = single == 2;           // single: 0 = split-f16 (three passes), 1 = plain f16 operands (RLCF_PREC_F16), 2 = split-f16 with an all-zero W lo part (two passes)
@@ -1818,11 +1155,6 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
     static int wpk_on = -1;
     if (wpk_on < 0) { const char* e = getenv("RLCF_X3_WPK"); wpk_on = e ? atoi(e) : 1; }
     const bool wpk_ok = wlo0 && next.wpk && wpk_on && K % 64 == 0 && (size_t)N * K < ((size_t)1 << 31);
-    // stream-K scratch (caller-owned, X3_WS_BYTES): slabs from the start of the workspace, flag words in its last X3_SK_FLAG_BYTES;
-    // *sk_epoch = the caller's launch counter for THIS workspace (0: flags not yet zeroed)
-    const bool sk_avail = sk_epoch && splitk_ws && splitk_ws_bytes >= (size_t)X3_SK_FLAG_BYTES + 8 * (size_t)X3_SK_SLAB_BYTES;
-    unsigned* sk_flags = sk_avail ? (unsigned*)((char*)splitk_ws + splitk_ws_bytes - X3_SK_FLAG_BYTES) : nullptr;
-    if (sk_avail) splitk_ws_bytes -= X3_SK_FLAG_BYTES;
     RLCF_ARG_CHECK(Ahi && Alo && Whi && Wlo && (C || (Chi && (Clo || single))));
     if (single) {       // plain f16 operands: a row of K halves == an interleaved pair row of K/2 logical columns (see GemmX3Args)
         RLCF_ARG_CHECK(K % 64 == 0 && Alo == (const void*)((const _Float16*)Ahi + 32) && Wlo == (const void*)((const _Float16*)Whi + 32));
@@ -1837,7 +1169,6 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
     g.kstep = (Alo == (const void*)((const _Float16*)Ahi + 32)) ? 64 : X3_BK;     // interleaved [hi32|lo32] blocks
     RLCF_ARG_CHECK((g.kstep == 64) == (Wlo == (const void*)((const _Float16*)Whi + 32)));   // both operands in the same layout
     const size_t sh = (size_t)2 * 4 * X3_TILE * sizeof(_Float16);
-#define X3_LDS(fn, bytes) do { int rc_ = rlcf_func_lds((const void*)(fn), (bytes)); if (rc_ != RLCF_OK) return rc_; } while (0)
     const int blocks2 = ((M + V2_BM - 1) / V2_BM) * ((N + V2_BN - 1) / V2_BN);
     static int force = -1;                                   // RLCF_X3_KERNEL=1|2 pins a variant (benchmarks)
     if (force < 0) { const char* e = getenv("RLCF_X3_KERNEL"); force = e ? atoi(e) : 0; }
@@ -1866,28 +1197,7 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount;
         if (ncu <= 0) ncu = 256;
     }
-    // Stream-K tail (see the kernel): the tiles of the last, partly filled round are shared out over the CUs by K steps.  Its cost in
-    // tile rounds = (K steps of the longest range + ~5 steps' worth of second launch and slab hand-over) / (nk + ~3 for a whole tile's
-    // epilogue).  MEASURED SLOWER THAN THE PLAIN LAUNCH on every shape tried (profiles/r4_gemm_tile_overhead.txt: one image's token
-    // matrix, 150 tiles on 256 CUs: 63.5 -> 100.5 us; out_proj at 20 images per pass, 11.54 rounds: 898 -> 943 us) — the partial tiles
-    // are 256 KB each, a round's worth of them is 30-64 MB written through to memory and read back, ~25 us of the chip's bandwidth
-    // against the ~35 us the balanced tail saves — so it is OFF by default; RLCF_X3_SK=1 switches it on (correct, bit-reproducible)
-    static int sk_mode = -1;
-    if (sk_mode < 0) { const char* e = getenv("RLCF_X3_SK"); sk_mode = e ? atoi(e) : 0; }
-    int sk_first = 0, sk_blocks = 0;
-    double cost3 = (double)((blocks3 + ncu - 1) / ncu);
-    {
-        const int nkt3 = K / X3_BK, R = blocks3 % ncu, min_steps = 6;
-        if (sk_mode && sk_avail && !single && g.kstep == 64 && v2_ok && ncu % 8 == 0 && ncu <= 256 && R > 0 && blocks3 >= 64 && nkt3 >= 2 * min_steps) {
-            int S = std::min(ncu, 8 * (int)((long)R * nkt3 / (8 * min_steps)));
-            S = std::min(S, (int)(std::min<size_t>(X3_SK_MAX_BLOCKS, splitk_ws_bytes / X3_SK_SLAB_BYTES) / 8 * 8));
-            if (S >= 8 * ((R + 7) / 8)) {                    // every range <= nk units: at most two tiles each
-                const int per = (((R + 7) / 8) * nkt3 + S / 8 - 1) / (S / 8);       // the longest range (the chunk with the most tiles)
-                const double tail = (per + 5.0) / (nkt3 + 3.0);
-                if (tail < 0.9) { sk_first = blocks3 - R; sk_blocks = S; cost3 = (double)(blocks3 / ncu) + tail; }
-            }
-        }
-    }
+    const double cost3 = (double)((blocks3 + ncu - 1) / ncu);
     // (0.62 since round 4, re-measured with W from HBM: [12608, 3072, 768] 5 rounds of 256x128 = 181.6 us against 3 rounds of 256x256 =
     // 175.0 us; [81900, 512, 512] 151.2 against 138.3 us; [81900, 512, 2048] 482 against 452 us — tools/gemm_mid_bench.py)
     const double cost2 = 0.62 * (double)((blocks2 + ncu - 1) / ncu);
@@ -1900,25 +1210,17 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
     if (mt3 < 0) { const char* e = getenv("RLCF_X3_MT3"); mt3 = e ? atoi(e) : 1; }
     const int blocks3h = ((M + 191) / 192) * ((N + V3_BN - 1) / V3_BN);
     const double cost3h = 0.78 * (double)((blocks3h + ncu - 1) / ncu);
-    const bool pick3h = v2_ok && !single && g.kstep == 64 && sk_blocks == 0 && force == 0 && blocks3h >= 128 && blocks2 >= 256 && !(C && Chi && residual) &&      // (conv3's f32 + pairs + identity epilogue: slower there)
-                       
+    const bool pick3h = v2_ok && !single && g.kstep == 64 && force == 0 && blocks3h >= 128 && blocks2 >= 256 && !(C && Chi && residual) &&      // (conv3's f32 + pairs + identity epilogue: slower there)
                         (mt3 == 2 || (mt3 == 1 && cost3h < 0.97 * std::min(cost3, blocks2 >= 256 ? cost2 : cost3)));
     if (pick3h) {
         const size_t sh3 = (size_t)8 * 64 * 68 * sizeof(float) > (size_t)2 * V3_STAGE ? (size_t)8 * 64 * 68 * sizeof(float) : (size_t)2 * V3_STAGE;
+        g_last_x3_variant = 5;
         if (wlo0 && wpk_ok) {
             g.Wpk = next.wpk; g.ldwpk = K;
-            X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, false, 3, 2>), sh3);
-            gemm_nt_f16x3_v3i_kernel<false, false, false, 3, 2><<<dim3(blocks3h), dim3(512), sh3, st>>>(g);
-        } else if (wlo0) {
-            X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, false, 3, 1>), sh3);
-            gemm_nt_f16x3_v3i_kernel<false, false, false, 3, 1><<<dim3(blocks3h), dim3(512), sh3, st>>>(g);
-        } else {
-        X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, false, 3>), sh3);
-        gemm_nt_f16x3_v3i_kernel<false, false, false, 3><<<dim3(blocks3h), dim3(512), sh3, st>>>(g);
+            return x3_launch(gemm_nt_f16x3_v3i_kernel<false, false, 3, 2>, dim3(blocks3h), 512, sh3, st, g);
         }
-        g_last_x3_variant = 5;
-        RLCF_LAUNCH_CHECK();
-        return RLCF_OK;
+        if (wlo0) return x3_launch(gemm_nt_f16x3_v3i_kernel<false, false, 3, 1>, dim3(blocks3h), 512, sh3, st, g);
+        return x3_launch(gemm_nt_f16x3_v3i_kernel<false, false, 3>, dim3(blocks3h), 512, sh3, st, g);
     }
     // RLCF_PREC_F16 at the big-tile regime: the dedicated single-pass kernel (gemm_f16.hip) instead of the K/2 alias of the pair kernels
     if (single && force == 0 && v2_ok && blocks2 >= 256 && cost3 <= cost2 &&
@@ -1927,81 +1229,29 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
         g_last_x3_variant = 3;
         return rc;
     }
-    const bool pick3 = (blocks2 >= 256 || sk_blocks > 0) && cost3 <= cost2;
+    const bool pick3 = blocks2 >= 256 && cost3 <= cost2;
     // smallest grid of 256x128 tiles that takes the 8-wave kernel: 160 (two waves per SIMD on 160+ CUs beat one wave per SIMD on twice as
     // many 128x128 workgroups: [4095, 1536, 512] 30.8 -> 27.3 us; below ~100 tiles the small tile wins).  RLCF_X3_V2MIN=256: the old rule
     static int v2min = -1;
     if (v2min < 0) { const char* e = getenv("RLCF_X3_V2MIN"); v2min = e ? atoi(e) : 160; }
-    // RLCF_X3_V4=1: the 4-wave form of the 256x256 tile where it applies (interleaved pairs, compile-time epilogues)
-    static int v4 = -1;
-    if (v4 < 0) { const char* e = getenv("RLCF_X3_V4"); v4 = e ? atoi(e) : 0; }
-    {
-        const bool f32o = C != nullptr, pair = Chi != nullptr, res = residual != nullptr;
-        const bool fast = !amax_out && !alpha_dev && !aux && !nofast &&
-                          ((epilogue == RLCF_EPI_NONE && f32o && !pair) || (epilogue == RLCF_EPI_QUICKGELU && !f32o && pair && !res) ||
-                           (epilogue == RLCF_EPI_NONE && !f32o && pair && !res));
-        if (v4 && v2_ok && !single && g.kstep == 64 && fast && (force == 3 || (force == 0 && pick3))) {
-            const size_t sh4 = (size_t)5 * 32768;
-            X3_LDS(gemm_nt_f16x3_v4_kernel<0>, sh4);
-            X3_LDS(gemm_nt_f16x3_v4_kernel<1>, sh4);
-            X3_LDS(gemm_nt_f16x3_v4_kernel<2>, sh4);
-            if (v4 == 2) gemm_nt_f16x3_v4_kernel<1><<<dim3(blocks3), dim3(256), sh4, st>>>(g);
-            else if (v4 == 3) gemm_nt_f16x3_v4_kernel<2><<<dim3(blocks3), dim3(256), sh4, st>>>(g);
-            else gemm_nt_f16x3_v4_kernel<0><<<dim3(blocks3), dim3(256), sh4, st>>>(g);
-            g_last_x3_variant = 3;
-            RLCF_LAUNCH_CHECK();
-            return RLCF_OK;
-        }
-    }
     if (v2_ok && (force == 3 || (force == 0 && pick3))) {
         const size_t sh3 = (size_t)8 * 64 * 68 * sizeof(float) > (size_t)2 * V3_STAGE ? (size_t)8 * 64 * 68 * sizeof(float) : (size_t)2 * V3_STAGE;
-        if (g.kstep == 64 && single) {
-            X3_LDS(gemm_nt_f16x3_v3i_kernel<true>, sh3);
-            gemm_nt_f16x3_v3i_kernel<true><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-        } else if (g.kstep == 64 && sk_blocks > 0) {
-            if (*sk_epoch == 0) RLCF_HIP_CHECK(hipMemsetAsync(sk_flags, 0, X3_SK_FLAG_BYTES, st));      // first use of this workspace
-            if (++*sk_epoch == 0) { RLCF_HIP_CHECK(hipMemsetAsync(sk_flags, 0, X3_SK_FLAG_BYTES, st)); *sk_epoch = 1; }     // (wrapped)
-            g.sk_first = sk_first; g.sk_blocks = sk_blocks; g.sk_epoch = *sk_epoch; g.sk_flags = sk_flags; g.sk_ws = splitk_ws;
-            X3_LDS(gemm_nt_f16x3_v3i_kernel<false>, sh3);
-            X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, true>), sh3);
-            // whole-tile workgroups for the full rounds, then the stream-K launch for the rest (first pieces, then second pieces)
-            if (sk_first > 0) gemm_nt_f16x3_v3i_kernel<false><<<dim3(sk_first), dim3(512), sh3, st>>>(g);
-            gemm_nt_f16x3_v3i_kernel<false, false, true><<<dim3(2 * sk_blocks), dim3(512), sh3, st>>>(g);
-        } else if (g.kstep == 64 && wlo0 && wpk_ok) {
-            g.Wpk = next.wpk; g.ldwpk = K;
-            X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, false, 4, 2>), sh3);
-            gemm_nt_f16x3_v3i_kernel<false, false, false, 4, 2><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-        } else if (g.kstep == 64 && wlo0) {
-            X3_LDS((gemm_nt_f16x3_v3i_kernel<false, false, false, 4, 1>), sh3);
-            gemm_nt_f16x3_v3i_kernel<false, false, false, 4, 1><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-        } else if (g.kstep == 64) {
-            X3_LDS(gemm_nt_f16x3_v3i_kernel<false>, sh3);
-            gemm_nt_f16x3_v3i_kernel<false><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-        } else {
-            X3_LDS(gemm_nt_f16x3_v3_kernel, sh3);
-            gemm_nt_f16x3_v3_kernel<<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-        }
         g_last_x3_variant = 3;
-        RLCF_LAUNCH_CHECK();
-        return RLCF_OK;
+        if (g.kstep != 64) return x3_launch(gemm_nt_f16x3_v3_kernel, dim3(blocks3), 512, sh3, st, g);
+        if (single) return x3_launch(gemm_nt_f16x3_v3i_kernel<true>, dim3(blocks3), 512, sh3, st, g);
+        if (wlo0 && wpk_ok) {
+            g.Wpk = next.wpk; g.ldwpk = K;
+            return x3_launch(gemm_nt_f16x3_v3i_kernel<false, false, 4, 2>, dim3(blocks3), 512, sh3, st, g);
+        }
+        if (wlo0) return x3_launch(gemm_nt_f16x3_v3i_kernel<false, false, 4, 1>, dim3(blocks3), 512, sh3, st, g);
+        return x3_launch(gemm_nt_f16x3_v3i_kernel<false>, dim3(blocks3), 512, sh3, st, g);
     }
     if (v2_ok && (force == 2 || (force == 0 && blocks2 >= v2min))) {
         const size_t sh2 = (size_t)3 * V2_STAGE;
-        if (single) {
-            X3_LDS((gemm_nt_f16x3_v2_kernel<4, true>), sh2);
-            gemm_nt_f16x3_v2_kernel<4, true><<<dim3(blocks2), dim3(512), sh2, st>>>(g);
-        } else {
-            if (wlo0) {
-                X3_LDS((gemm_nt_f16x3_v2_kernel<4, false, 2, true>), sh2);
-                gemm_nt_f16x3_v2_kernel<4, false, 2, true><<<dim3(blocks2), dim3(512), sh2, st>>>(g);
-            } else {
-            X3_LDS((gemm_nt_f16x3_v2_kernel<4, false>), sh2);
-            gemm_nt_f16x3_v2_kernel<4, false><<<dim3(blocks2), dim3(512), sh2, st>>>(g);
-            }
-        }
         g_last_x3_variant = 2;
-        RLCF_LAUNCH_CHECK();
-        return RLCF_OK;
+        if (single) return x3_launch(gemm_nt_f16x3_v2_kernel<4, true>, dim3(blocks2), 512, sh2, st, g);
+        if (wlo0) return x3_launch(gemm_nt_f16x3_v2_kernel<4, false, 2, true>, dim3(blocks2), 512, sh2, st, g);
+        return x3_launch(gemm_nt_f16x3_v2_kernel<4, false>, dim3(blocks2), 512, sh2, st, g);
     }
     static int nov2s = -1;                                   // RLCF_X3_NOV2S=1: small grids back on the register-staged kernel
     if (nov2s < 0) { const char* e = getenv("RLCF_X3_NOV2S"); nov2s = e ? atoi(e) : 0; }
@@ -2021,13 +1271,6 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
         const bool eight = v2s8 && !single && !half_m;
         const int blocks_h = ((M + 63) / 64) * ((N + V2_BN - 1) / V2_BN);
         const int nblk = half_m ? blocks_h : blocks2s;           // workgroups per K slice
-        if (single) X3_LDS((gemm_nt_f16x3_v2_kernel<2, true>), sh2s);
-        else if (eight && wlo0) X3_LDS((gemm_nt_f16x3_v2_kernel<4, false, 1, true>), sh2s);
-        else if (eight) X3_LDS((gemm_nt_f16x3_v2_kernel<4, false, 1>), sh2s);
-        else if (half_m && wlo0) X3_LDS((gemm_nt_f16x3_v2_kernel<2, false, 1, true>), sh2s);
-        else if (half_m) X3_LDS((gemm_nt_f16x3_v2_kernel<2, false, 1>), sh2s);
-        else if (wlo0) X3_LDS((gemm_nt_f16x3_v2_kernel<2, false, 2, true>), sh2s);
-        else X3_LDS((gemm_nt_f16x3_v2_kernel<2, false>), sh2s);
         // few tiles and a long K loop (one image's token matrix against a W x 4W / W x 3W weight): split the K loop over blockIdx.y
         // and finish in a reduce + epilogue pass (RLCF_X3_NOSPLITK=1 switches it off)
         static int nosplit = -1;
@@ -2049,15 +1292,17 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
         }
         if (ksplit > 1 && (!splitk_ws || (size_t)ksplit * M * N * sizeof(float) > splitk_ws_bytes)) ksplit = 1;
         g.ksplit = ksplit; g.ws = splitk_ws;
-        if (single) gemm_nt_f16x3_v2_kernel<2, true><<<dim3(blocks2s, ksplit), dim3(256), sh2s, st>>>(g);
-        else if (eight && wlo0) gemm_nt_f16x3_v2_kernel<4, false, 1, true><<<dim3(blocks2s, ksplit), dim3(512), sh2s, st>>>(g);
-        else if (eight) gemm_nt_f16x3_v2_kernel<4, false, 1><<<dim3(blocks2s, ksplit), dim3(512), sh2s, st>>>(g);
-        else if (half_m && wlo0) gemm_nt_f16x3_v2_kernel<2, false, 1, true><<<dim3(blocks_h, ksplit), dim3(256), sh2s, st>>>(g);
-        else if (half_m) gemm_nt_f16x3_v2_kernel<2, false, 1><<<dim3(blocks_h, ksplit), dim3(256), sh2s, st>>>(g);
-        else if (wlo0) gemm_nt_f16x3_v2_kernel<2, false, 2, true><<<dim3(blocks2s, ksplit), dim3(256), sh2s, st>>>(g);
-        else gemm_nt_f16x3_v2_kernel<2, false><<<dim3(blocks2s, ksplit), dim3(256), sh2s, st>>>(g);
         g_last_x3_variant = 1;
-        RLCF_LAUNCH_CHECK();
+        const dim3 grid(nblk, ksplit);
+        int rc;
+        if (single) rc = x3_launch(gemm_nt_f16x3_v2_kernel<2, true>, grid, 256, sh2s, st, g);
+        else if (eight && wlo0) rc = x3_launch(gemm_nt_f16x3_v2_kernel<4, false, 1, true>, grid, 512, sh2s, st, g);
+        else if (eight) rc = x3_launch(gemm_nt_f16x3_v2_kernel<4, false, 1>, grid, 512, sh2s, st, g);
+        else if (half_m && wlo0) rc = x3_launch(gemm_nt_f16x3_v2_kernel<2, false, 1, true>, grid, 256, sh2s, st, g);
+        else if (half_m) rc = x3_launch(gemm_nt_f16x3_v2_kernel<2, false, 1>, grid, 256, sh2s, st, g);
+        else if (wlo0) rc = x3_launch(gemm_nt_f16x3_v2_kernel<2, false, 2, true>, grid, 256, sh2s, st, g);
+        else rc = x3_launch(gemm_nt_f16x3_v2_kernel<2, false>, grid, 256, sh2s, st, g);
+        if (rc != RLCF_OK) return rc;
         if (ksplit > 1) {
             const long groups = (long)M * (N / 4);
             gemm_x3_splitk_reduce_kernel<<<dim3((unsigned)std::min<long>((groups + 255) / 256, 2048)), dim3(256), 0, st>>>(g);
@@ -2066,16 +1311,9 @@ int launch_gemm_f16x3(const void* Ahi, const void* Alo, int lda, const void* Whi
         return RLCF_OK;
     }
     const int blocks = ((M + X3_BM - 1) / X3_BM) * ((N + X3_BN - 1) / X3_BN);
-    if (single) {
-        X3_LDS(gemm_nt_f16x3_kernel<true>, sh);
-        gemm_nt_f16x3_kernel<true><<<dim3(blocks), dim3(256), sh, st>>>(g);
-    } else {
-        X3_LDS(gemm_nt_f16x3_kernel<false>, sh);
-        gemm_nt_f16x3_kernel<false><<<dim3(blocks), dim3(256), sh, st>>>(g);
-    }
     g_last_x3_variant = 1;
-    RLCF_LAUNCH_CHECK();
-    return RLCF_OK;
+    if (single) return x3_launch(gemm_nt_f16x3_kernel<true>, dim3(blocks), 256, sh, st, g);
+    return x3_launch(gemm_nt_f16x3_kernel<false>, dim3(blocks), 256, sh, st, g);
 }
 
 // Implicit 3x3 convolution (stride 1, pad 1) on the 256x256 kernel: act = the NHWC activation [n*H*W, Cin] as interleaved operand
@@ -2107,20 +1345,13 @@ int launch_gemm_f16x3_conv3x3(const void* act_pairs, int n, int H, int W, int Ci
     const size_t sh3 = (size_t)8 * 64 * 68 * sizeof(float) > (size_t)2 * V3_STAGE ? (size_t)8 * 64 * 68 * sizeof(float) : (size_t)2 * V3_STAGE;
     static int wpk_on = -1;
     if (wpk_on < 0) { const char* e = getenv("RLCF_X3_WPK"); wpk_on = e ? atoi(e) : 1; }
+    g_last_x3_variant = 3;
     if (wlo0 && next.wpk && wpk_on && K % 64 == 0 && (size_t)Cout * K < ((size_t)1 << 31)) {       // hi-only W rows, two K tiles per row block
         g.Wpk = next.wpk; g.ldwpk = K;
-        { int rc_ = rlcf_func_lds((const void*)(gemm_nt_f16x3_v3i_kernel<false, true, false, 4, 2>), sh3); if (rc_ != RLCF_OK) return rc_; }
-        gemm_nt_f16x3_v3i_kernel<false, true, false, 4, 2><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-    } else if (wlo0) {
-        { int rc_ = rlcf_func_lds((const void*)(gemm_nt_f16x3_v3i_kernel<false, true, false, 4, 1>), sh3); if (rc_ != RLCF_OK) return rc_; }
-        gemm_nt_f16x3_v3i_kernel<false, true, false, 4, 1><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
-    } else {
-    { int rc_ = rlcf_func_lds((const void*)(gemm_nt_f16x3_v3i_kernel<false, true>), sh3); if (rc_ != RLCF_OK) return rc_; }
-    gemm_nt_f16x3_v3i_kernel<false, true><<<dim3(blocks3), dim3(512), sh3, st>>>(g);
+        return x3_launch(gemm_nt_f16x3_v3i_kernel<false, true, 4, 2>, dim3(blocks3), 512, sh3, st, g);
     }
-    g_last_x3_variant = 3;
-    RLCF_LAUNCH_CHECK();
-    return RLCF_OK;
+    if (wlo0) return x3_launch(gemm_nt_f16x3_v3i_kernel<false, true, 4, 1>, dim3(blocks3), 512, sh3, st, g);
+    return x3_launch(gemm_nt_f16x3_v3i_kernel<false, true>, dim3(blocks3), 512, sh3, st, g);
 }
 
 // does every element of w * scale sit on the f16 grid (its lo half is zero)?  flag[0] |= 1 otherwise

@@ -3,13 +3,6 @@
 #pragma once
 #include "kernels.h"
 
-// MFMA shape of the split-f16 kernel family (gemm_f16x3.hip: the register-staged kernel, v2, v3, v3i): 1 = v_mfma_f32_16x16x32_f16, one
-// instruction per product and 32-wide K block; 0 = v_mfma_f32_32x32x16_f16, two k-substeps of 16 (`make X3_MFMA16=0`: the A/B partner).
-// Compile time only: the two shapes sum inside the instruction in different orders, so every kernel of the family moves together.
-#ifndef X3_MFMA16
-#define X3_MFMA16 1
-#endif
-
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -38,12 +31,10 @@ struct GemmX3Args {
     int tile_group;                    // 256x256 interleaved kernel: M tiles per scheduling group (0 = 8)
     const float* out_scale_dev;        // optional device scalar: the split output carries C * out_scale_dev[0] (a power of two chosen from
                                        // an upper bound of |C| before the launch: the consumer undoes it through ITS alpha_dev)
-    // stream-K tail of the 256x256 interleaved kernel (launch_gemm_f16x3): tiles [0, sk_first) of the linear order are whole-tile
-    // workgroups of the plain launch; the K steps of the remaining tiles are shared by the 2 * sk_blocks workgroups of the SK launch
-    int sk_first, sk_blocks;
-    unsigned sk_epoch;                 // value a "partial tile published" flag carries in THIS launch (flags are never reset)
-    unsigned* sk_flags;                // [X3_SK_MAX_BLOCKS] + [1] time-out marker
-    float* sk_ws;                      // [sk_blocks][256 x 256] raw partial accumulators, register layout
+    // single-pass f16 kernel only (gemm_f16.hip, gemm_nt_f16_pp_kernel):
+    int pp_desync;                     // RLCF_F16_PP_DESYNC=P: |P| start-time cohorts (P > 1: by the workgroup's index inside its XCD; P < -1: whole
+                                       // XCDs as cohorts; 0 / 1 / -1: all workgroups start together)
+    unsigned pp_nt;                    // RLCF_F16_PP_NT: non-temporal output stores
     // Output scale of a pair-emitting convolution chosen INSIDE the launch (round 5; before: conv_bound_scale_kernel, a one-thread launch
     // in front of every such GEMM — 136 launches per test image at RN50x64): bnd_in / bnd_res = device scalars max|input| and
     // max|identity| (complete before this launch), bnd_gain / bnd_bmax = host constants of the folded convolution; every thread derives
@@ -68,9 +59,6 @@ struct GemmX3Args {
     // instructions per wave and K tile) and no zero lo half travels
     const _Float16* Wpk; int ldwpk;
 };
-#define X3_SK_MAX_BLOCKS 1024
-#define X3_SK_FLAG_BYTES 8192                                   // flags + time-out word, at the end of the workspace
-#define X3_SK_SLAB_BYTES 262144
 // SINGLE (template flag of the kernels): plain f16 operands, ONE MFMA per product (RLCF_PREC_F16 — the arithmetic of the reference's
 // own fp16-autocast GPU path, tpt_cls_rl.py:52; NOT f32-grade).  A plain f16 row of K halves has exactly the memory layout of an
 // interleaved pair row of K/2 logical columns (every 128-B block = 32 "hi" + 32 "lo" halves), so the kernels run unchanged with
@@ -106,10 +94,8 @@ __device__ __forceinline__ void x3_publish_scale(const GemmX3Args& g) {
 // are parked and combined in registers (no store yet); then the 16 rows stream out back to back.  Each wave parks and re-reads only
 // its own LDS slice, so one barrier (the ring is no longer read) is all the synchronisation there is.
 // One call = the 64x64 slab of one wave: a0..a3 = accumulator tiles (i, j) = (0,0) (0,1) (1,0) (1,1); row0 / col0 = its origin.
-// LEAN (the experimental 4-wave kernel, which has no register to spare): the forward towers' form only -- host alpha, no ReLU, no
-// max|C|, no output scale
 // The PARK step alone depends on the accumulator layout (parkfn: the two overloads of x3_epilogue_slab below).
-template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN, int NIT, class PARKFN>
+template <int EPI, bool RES, bool F32OUT, bool PAIR, int NIT, class PARKFN>
 __device__ __forceinline__ void x3_epilogue_slab_impl(const GemmX3Args& g, const PARKFN& parkfn, float* park, int row0, int col0, int lane, float& am) {
     constexpr int ELD = 68;
     const int c4 = (lane & 15) * 4, rsub = lane >> 4;
@@ -118,14 +104,14 @@ __device__ __forceinline__ void x3_epilogue_slab_impl(const GemmX3Args& g, const
     const int colc = colok ? col : 0;
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (g.bias) bv = *(const float4*)(g.bias + colc);
-    const float al = LEAN ? g.alpha : x3_alpha(g);         // (alpha_dev: the device-side undo of a data-dependent operand scale)
+    const float al = x3_alpha(g);         // (alpha_dev: the device-side undo of a data-dependent operand scale)
     // alpha times the optional per-column factor (GemmX3Args::col_scale: the BatchNorm scale of an unfolded ResNet convolution; exactly alpha when none)
     float4 alc = make_float4(al, al, al, al);
-    if (!LEAN && g.col_scale) { const float4 cs4 = *(const float4*)(g.col_scale + colc); alc = make_float4(al * cs4.x, al * cs4.y, al * cs4.z, al * cs4.w); }
-    const bool relu = !LEAN && g.epilogue == RLCF_EPI_RELU;     // ResNet convolutions: ReLU after the identity add (wave-uniform, one select per value)
-    const float os = (!LEAN && PAIR) ? x3_out_scale(g) : 1.0f;
-    const bool want_amax = !LEAN && g.amax_out != nullptr;
-    const bool nt = !LEAN && (g.no_fast_epi & 2);             // non-temporal output stores (RLCF_X3_NT=0: default cache policy, A/B)
+    if (g.col_scale) { const float4 cs4 = *(const float4*)(g.col_scale + colc); alc = make_float4(al * cs4.x, al * cs4.y, al * cs4.z, al * cs4.w); }
+    const bool relu = g.epilogue == RLCF_EPI_RELU;      // ResNet convolutions: ReLU after the identity add (wave-uniform, one select per value)
+    const float os = PAIR ? x3_out_scale(g) : 1.0f;
+    const bool want_amax = g.amax_out != nullptr;
+    const bool nt = (g.no_fast_epi & 2) != 0;      // non-temporal output stores (RLCF_X3_NT=0: default cache policy, A/B)
     const int ocol = g.c_il ? (((colc >> 5) << 6) | (colc & 31)) : colc;
     const int rbase = row0 + rsub;
     float4 rr[16];
@@ -141,7 +127,7 @@ __device__ __forceinline__ void x3_epilogue_slab_impl(const GemmX3Args& g, const
     // Now the 16 lanes of a row swap with lane ^ 8 what the partner's line needs (the lanes of block 0 send their lo halves and receive block
     // 1's hi halves): instruction A writes the whole line of block 0, instruction B the whole line of block 1 — each line requested once.
     // Same values, same bits, same number of store instructions.  RLCF_X3_LINEST=0: off.
-    const bool line_ok = PAIR && !RES && !F32OUT && !LEAN && g.c_il && g.Clo == g.Chi + 32 && !(g.no_fast_epi & 4) && col0 + 64 <= g.N && (g.ldch & 3) == 0;
+    const bool line_ok = PAIR && !RES && !F32OUT && g.c_il && g.Clo == g.Chi + 32 && !(g.no_fast_epi & 4) && col0 + 64 <= g.N && (g.ldch & 3) == 0;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const float4 a4 = *(const float4*)(park + (it * 4 + rsub) * ELD + c4);
@@ -223,10 +209,10 @@ __device__ __forceinline__ void x3_epilogue_slab_impl(const GemmX3Args& g, const
     }
 }
 // 32x32 accumulator tiles: a0..a3 = tiles (i, j) = (0,0) (0,1) (1,0) (1,1) of the slab
-template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN = false, int NIT = 16>
+template <int EPI, bool RES, bool F32OUT, bool PAIR, int NIT = 16>
 __device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x16& a0, const f32x16& a1, const f32x16& a2, const f32x16& a3,
                                                  float* park, int row0, int col0, int lane, float& am) {
-    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, LEAN, NIT>(g, [&]() {
+    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, NIT>(g, [&]() {
         constexpr int ELD = 68;
         const int l32 = lane & 31, h = lane >> 5;
 #pragma unroll
@@ -250,9 +236,9 @@ __device__ __forceinline__ void x3_park16(float* park, const f32x4* a, int lane)
 #pragma unroll
             for (int r = 0; r < 4; ++r) p[(16 * ti + r) * ELD + 16 * tj] = a[ti * 4 + tj][r];
 }
-template <int EPI, bool RES, bool F32OUT, bool PAIR, bool LEAN = false, int NIT = 16>
+template <int EPI, bool RES, bool F32OUT, bool PAIR, int NIT = 16>
 __device__ __forceinline__ void x3_epilogue_slab(const GemmX3Args& g, const f32x4* a, float* park, int row0, int col0, int lane, float& am) {
-    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, LEAN, NIT>(g, [&]() { x3_park16<NIT / 4>(park, a, lane); }, park, row0, col0, lane, am);
+    x3_epilogue_slab_impl<EPI, RES, F32OUT, PAIR, NIT>(g, [&]() { x3_park16<NIT / 4>(park, a, lane); }, park, row0, col0, lane, am);
 }
 // which specialisation (wave-uniform): 0 = none (generic epilogue), 1 = f32 out, 2 = f32 out + residual, 3 = QuickGELU -> operand pair,
 // 4 = operand pair only (in_proj of the image towers: Q / K / V go to the attention kernel as f16 pairs, attention_pair.hip)
@@ -280,10 +266,10 @@ __device__ __forceinline__ int x3_epilogue_kind(const GemmX3Args& g) {
 
 #define X3_EPILOGUE_HALFSLAB(kind, ...)                                                                                  \
     {                                                                                                                    \
-        if ((kind) == 1) x3_epilogue_slab<RLCF_EPI_NONE, false, true, false, false, 8>(__VA_ARGS__);                     \
-        else if ((kind) == 2) x3_epilogue_slab<RLCF_EPI_NONE, true, true, false, false, 8>(__VA_ARGS__);                 \
-        else if ((kind) == 3) x3_epilogue_slab<RLCF_EPI_QUICKGELU, false, false, true, false, 8>(__VA_ARGS__);           \
-        else if ((kind) == 5) x3_epilogue_slab<RLCF_EPI_NONE, true, true, true, false, 8>(__VA_ARGS__);                  \
-        else x3_epilogue_slab<RLCF_EPI_NONE, false, false, true, false, 8>(__VA_ARGS__);                                 \
+        if ((kind) == 1) x3_epilogue_slab<RLCF_EPI_NONE, false, true, false, 8>(__VA_ARGS__);                            \
+        else if ((kind) == 2) x3_epilogue_slab<RLCF_EPI_NONE, true, true, false, 8>(__VA_ARGS__);                        \
+        else if ((kind) == 3) x3_epilogue_slab<RLCF_EPI_QUICKGELU, false, false, true, 8>(__VA_ARGS__);                  \
+        else if ((kind) == 5) x3_epilogue_slab<RLCF_EPI_NONE, true, true, true, 8>(__VA_ARGS__);                         \
+        else x3_epilogue_slab<RLCF_EPI_NONE, false, false, true, 8>(__VA_ARGS__);                                        \
     }
 

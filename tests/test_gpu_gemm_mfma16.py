@@ -1,7 +1,7 @@
-"""The split-f16 GEMM family on the 16x16x32 MFMA shape (gemm_f16x3.hip, X3_MFMA16): a new fragment map, a new accumulator map and
+"""The split-f16 GEMM family on the 16x16x32 MFMA shape (gemm_f16x3.hip): a new fragment map, a new accumulator map and
 a new park step in every kernel the launcher can pick.  Everything goes through rlcf_gemm_f16x3 on interleaved operand pairs; the
-shapes are chosen so that the launcher's own rules select each form (which kernel ran is not asserted).  The tests hold for both
-settings of X3_MFMA16."""
+shapes are chosen so that the launcher's own rules select each form (which kernel ran is not asserted).  The tests do not depend
+on the MFMA shape: they held on the 32x32x16 form of the family as well."""
 import pytest
 import torch
 

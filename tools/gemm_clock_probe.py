@@ -1,5 +1,5 @@
-"""Sustained shader clock / socket power while one GEMM variant runs back to back (c_proj shape of ViT-B/16: M x 768 x 3072 + residual).
-RLCF_X3_V4 selects the variant (0 = 8-wave v3i, 1 = 4-wave v4, 2 = v4 without DMA, 3 = v4 without MFMAs).  Samples rocm-smi at ~4 Hz."""
+"""Sustained shader clock / socket power while the 256x256 split-f16 GEMM runs back to back (c_proj shape of ViT-B/16: M x 768 x 3072 +
+residual).  Samples rocm-smi at ~4 Hz."""
 import os, subprocess, sys, threading, time, json, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rlcf_amd import _lib as L
@@ -38,6 +38,6 @@ for _ in range(reps): run()
 e1.record(); torch.cuda.synchronize()
 stop = True; th.join()
 ms = e0.elapsed_time(e1) / reps
-print(f"variant RLCF_X3_V4={os.environ.get('RLCF_X3_V4', '0')}: {ms*1e3:.1f} us per launch, {2*M*N*K/ms/1e9:.1f} TF over {reps} launches; {len(samples)} samples")
+print(f"{ms*1e3:.1f} us per launch, {2*M*N*K/ms/1e9:.1f} TF over {reps} launches; {len(samples)} samples")
 mid = samples[len(samples) // 4: max(len(samples) // 4 + 1, 3 * len(samples) // 4)]
 for s_ in mid[:6]: print("  ", s_)

@@ -4,7 +4,7 @@ busy).  usage: python tools/r6_counters_summary.py [capture dir]"""
 import json, os, re, sys
 D = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/r6/final"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "gemm_nt_f16x3_v3i_kernel<false,false,false,4>"
+KERNEL = "gemm_nt_f16x3_v3i_kernel<false,false,4>"
 
 
 def table(path):
