@@ -419,6 +419,40 @@ typedef struct {                 /* every pointer optional (NULL = not wanted); 
  * test_time_tuning (:47-79), final one-view inference on views[0], top-5.  views [N,3,R,R]. */
 int rlcf_tta_sample(rlcf_engine*, const float* views, int N, const rlcf_tta_args* args,
                     const rlcf_tta_out* out, rlcf_stream stream);
+/* (ABI version 19) CoCoOp, the `--cocoop` branch of TPT/tpt_cls.py (TPT/clip/cocoop.py).
+ * rlcf_cocoop_ctx — the prompt generator, CoCoOpPromptLearner.forward(im_features, ctx_only=True) (cocoop.py:118-127), stateless:
+ *   out[r] = ctx + (W2 relu(W1 f_r + b1) + b2), the meta-net's output broadcast over the n_ctx rows; feats [n, D] (row stride ld >= D),
+ *   ctx [n_ctx, W], w1 [H, D], b1 [H], w2 [W, H], b2 [W] (nn.Linear layout; the reference's H is D / 16).  mean = 0: one prompt per
+ *   feature row, out [n, n_ctx, W]; mean != 0: the n rows are averaged first (gen_ctx(aug=False), cocoop.py:179), out [1, n_ctx, W].
+ *   One launch; sums in double, rounded to float once; fixed-order reductions, no atomics: two calls give the same bits and a row gives
+ *   the same bits alone as inside a batch.  H < 1, n < 1 (or > 65535), a row stride below D or a NULL pointer: RLCF_ERR_ARG.
+ * rlcf_engine_set_meta_net — device copies of the student's meta-net (w1 [H, embed_dim], w2 [text_width, H]).  The generator's ctx
+ *   parameter is the class bank's ctx_init (rlcf_engine_set_class_bank).  rlcf_cocoop_gen_ctx and rlcf_tta_sample_cocoop return
+ *   RLCF_ERR_STATE while no meta-net is set.
+ * rlcf_cocoop_gen_ctx — CoCoOpCLIP.gen_ctx(image, aug) (cocoop.py:172-182): one pass of the student image tower over views
+ *   [N, 3, R, R]; feats_raw_out [N, D] = the image features BEFORE the L2 normalisation, ctx_out [n_ctx, W] = the prompt generated from
+ *   row 0 (aug != 0) or from the mean over the rows (aug = 0).  Both outputs optional.
+ * rlcf_tta_sample_feats — the prompt step of rlcf_tta_sample from given un-normalised features [N, D] in place of views
+ *   (test_time_tuning on (image_feature, pgen_ctx) and the final call, TPT/tpt_cls.py:49-78,285-295; forward_ctx, cocoop.py:184-217):
+ *   the rows are L2-normalised, the prompt starts at args->ctx_in (required), then selection, rlcf_tpt_loss, the dense text backward
+ *   and AdamW with the GradScaler step skip, and out->final_logits / top5 on row 0 (unless skip_final).  Outputs as rlcf_tta_sample
+ *   fills them.  Accepted with RLCF_F_TPT only (the other losses read the views for the reward model's pass); tta_steps > 1 is
+ *   refused: at a second step the reference indexes its (features, ctx) tuple (TPT/tpt_cls.py:60) and stops with a TypeError.
+ * rlcf_tta_sample_cocoop — the loop body TPT/tpt_cls.py:280-297 with --cocoop and --tpt as ONE call: gen_ctx(views, aug = 1), the
+ *   step, the final logits; one image pass, no host synchronisation.  args->ctx_in must be NULL.  feats_raw_out [N, D] and ctx_gen_out
+ *   [n_ctx, W] (optional) as rlcf_cocoop_gen_ctx writes them; every output equals, bit for bit, that of rlcf_cocoop_gen_ctx followed
+ *   by rlcf_tta_sample_feats.  The AdamW of the reference's CoCoOp step is torch.optim.AdamW([pgen_ctx], args.lr): weight_decay 0.01.
+ * rlcf_l2norm_rows — out[r] = in[r] / |in[r]| for rows of `width` contiguous floats: the normalisation the engine applies to image
+ *   features (cocoop.py:158,208), stateless, for callers that hold un-normalised features (CoCoOpCLIP.forward_ctx / inference). */
+int rlcf_l2norm_rows(const float* in, float* out, int rows, int width, rlcf_stream stream);
+int rlcf_cocoop_ctx(const float* feats, int ld, int n, int mean, const float* ctx, int n_ctx, const float* w1, const float* b1,
+                    const float* w2, const float* b2, int D, int H, int W, float* out, rlcf_stream stream);
+int rlcf_engine_set_meta_net(rlcf_engine*, const float* w1, const float* b1, const float* w2, const float* b2, int H, rlcf_stream stream);
+int rlcf_cocoop_gen_ctx(rlcf_engine*, const float* views, int N, int aug, float* feats_raw_out, float* ctx_out, rlcf_stream stream);
+int rlcf_tta_sample_feats(rlcf_engine*, const float* feats_raw, int N, const rlcf_tta_args* args, const rlcf_tta_out* out,
+                          rlcf_stream stream);
+int rlcf_tta_sample_cocoop(rlcf_engine*, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out,
+                           float* feats_raw_out, float* ctx_gen_out, rlcf_stream stream);
 /* LayerNorm-tuning variant (TPT/tune_cls_rl.py with CLIPCLS_TTA(only_visual=True, only_norm=True),
  * custom_clip.py:364-497): the class text features are cached, the IMAGE encoder runs with grad and the tunable set is
  * every visual LayerNorm weight/bias, laid out [ln_pre.w, ln_pre.b, (ln_1.w, ln_1.b, ln_2.w, ln_2.b) x layers, ln_post.w,

@@ -126,6 +126,12 @@ SIGNATURES = {
     "rlcf_logits": (I, [P, P, I, P, I, P, P]),
     "rlcf_text_backward_dense": (I, [P, P, P, I, P, P, P]),
     "rlcf_tta_sample": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
+    "rlcf_cocoop_ctx": (I, [P, I, I, I, P, I, P, P, P, P, I, I, I, P, P]),
+    "rlcf_l2norm_rows": (I, [P, P, I, I, P]),
+    "rlcf_engine_set_meta_net": (I, [P, P, P, P, P, I, P]),
+    "rlcf_cocoop_gen_ctx": (I, [P, P, I, I, P, P, P]),
+    "rlcf_tta_sample_feats": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
+    "rlcf_tta_sample_cocoop": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P, P, P]),
     "rlcf_tta_batch": (I, [P, P, I, I, C.POINTER(TTAArgs), P, P, P]),
     "rlcf_tta_sample_ln": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
     "rlcf_tta_retrieval_image": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),

@@ -35,7 +35,7 @@ int rlcf_func_lds(const void* fn, size_t bytes) {
 extern "C" {
 
 const char* rlcf_last_error(void) { return g_err; }
-int rlcf_version(void) { return 18; }   // 18: rlcf_gemm_f16x3_grid_w (the two-pass split-f16 product as a stand-alone call); 17: the TPT baseline (rlcf_tpt_loss, RLCF_F_TPT on rlcf_tta_sample / _sample_ln / _sample_visual / _batch / _batch_ln: avg_entropy in place of the reward loss, an engine without a reward model); 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
+int rlcf_version(void) { return 19; }   // 19: CoCoOp (rlcf_cocoop_ctx, rlcf_l2norm_rows, rlcf_engine_set_meta_net, rlcf_cocoop_gen_ctx, rlcf_tta_sample_feats, rlcf_tta_sample_cocoop: the --cocoop branch of TPT/tpt_cls.py); 18: rlcf_gemm_f16x3_grid_w (the two-pass split-f16 product as a stand-alone call); 17: the TPT baseline (rlcf_tpt_loss, RLCF_F_TPT on rlcf_tta_sample / _sample_ln / _sample_visual / _batch / _batch_ln: avg_entropy in place of the reward loss, an engine without a reward model); 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
 //    // 2: rlcf_clip_cfg.vision_stages, reward slots, views, LN batch; 3: rlcf_tta_out.vis_*, rlcf_tta_sample_visual
 
 // ------------------------------------------------------------------ op level
@@ -494,6 +494,54 @@ int rlcf_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_ar
     RLCF_ARG_CHECK(e && views && args);
     TTA_CHECK(e, args, "rlcf_tta_sample", KINDS_RL_TPT, TTA_PROMPT);
     return engine_tta_sample(e, views, N, args, out, engine_stream(e, stream));
+}
+// ------------------------------------------------------------------ CoCoOp (ABI 19)
+int rlcf_cocoop_ctx(const float* feats, int ld, int n, int mean, const float* ctx, int n_ctx, const float* w1, const float* b1, const float* w2,
+                    const float* b2, int D, int H, int W, float* out, rlcf_stream stream) {
+    return launch_cocoop_ctx(feats, ld, n, mean, ctx, n_ctx, w1, b1, w2, b2, D, H, W, out, (hipStream_t)stream);
+}
+int rlcf_l2norm_rows(const float* in, float* out, int rows, int width, rlcf_stream stream) {
+    RLCF_ARG_CHECK(in && out && rows > 0 && width > 0);
+    return launch_l2norm_rows(in, out, nullptr, rows, width, (hipStream_t)stream);
+}
+int rlcf_engine_set_meta_net(rlcf_engine* e, const float* w1, const float* b1, const float* w2, const float* b2, int H, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && w1 && b1 && w2 && b2);
+    if (H < 1 || H > 4096) { rlcf_set_error("rlcf_engine_set_meta_net: H = %d hidden units (need 1 <= H <= 4096; the reference's is embed_dim / 16)", H); return RLCF_ERR_ARG; }
+    return engine_set_meta_net(e, w1, b1, w2, b2, H, engine_stream(e, stream));
+}
+int rlcf_cocoop_gen_ctx(rlcf_engine* e, const float* views, int N, int aug, float* feats_raw_out, float* ctx_out, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && views && N > 0 && N <= e->max_views);
+    return engine_cocoop_gen_ctx(e, views, N, aug, feats_raw_out, ctx_out, engine_stream(e, stream));
+}
+// the argument rules the two CoCoOp step entries share (before anything is launched; the argument rules come before the state rules)
+static int cocoop_step_args(const rlcf_engine* e, const rlcf_tta_args* a, int N, const char* entry) {
+    if (!(a->flags & RLCF_F_TPT)) {
+        rlcf_set_error("%s: only the TPT loss RLCF_F_TPT has a form here (the reward and distillation losses read the views for the reward model's pass; "
+                       "TPT/tpt_cls.py is the only script with a --cocoop branch)", entry);
+        return RLCF_ERR_ARG;
+    }
+    if (a->tta_steps < 0 || a->tta_steps > 1) {
+        rlcf_set_error("%s: tta_steps = %d: CoCoOp exists for 0 or 1 steps only (at a second step the reference indexes its (features, ctx) tuple, "
+                       "TPT/tpt_cls.py:60, and stops with a TypeError)", entry, a->tta_steps);
+        return RLCF_ERR_ARG;
+    }
+    if (N <= 0 || N > e->max_views) { rlcf_set_error("%s: N = %d rows (need 1 <= N <= max_views = %d)", entry, N, e->max_views); return RLCF_ERR_ARG; }
+    return RLCF_OK;
+}
+int rlcf_tta_sample_feats(rlcf_engine* e, const float* feats_raw, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && feats_raw && args);
+    { const int rc = cocoop_step_args(e, args, N, "rlcf_tta_sample_feats"); if (rc != RLCF_OK) return rc; }
+    if (!args->ctx_in) { rlcf_set_error("rlcf_tta_sample_feats: args->ctx_in (the starting prompt, e.g. rlcf_cocoop_gen_ctx's) is required"); return RLCF_ERR_ARG; }
+    TTA_CHECK(e, args, "rlcf_tta_sample_feats", LOSS_BIT(LOSS_TPT), TTA_PROMPT);
+    return engine_tta_sample_feats(e, feats_raw, N, args, out, engine_stream(e, stream));
+}
+int rlcf_tta_sample_cocoop(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, float* feats_raw_out,
+                           float* ctx_gen_out, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && views && args);
+    { const int rc = cocoop_step_args(e, args, N, "rlcf_tta_sample_cocoop"); if (rc != RLCF_OK) return rc; }
+    if (args->ctx_in) { rlcf_set_error("rlcf_tta_sample_cocoop: args->ctx_in must be NULL (the starting prompt is the one generated from views[0])"); return RLCF_ERR_ARG; }
+    TTA_CHECK(e, args, "rlcf_tta_sample_cocoop", LOSS_BIT(LOSS_TPT), TTA_PROMPT);
+    return engine_tta_sample_cocoop(e, views, N, args, out, feats_raw_out, ctx_gen_out, engine_stream(e, stream));
 }
 int rlcf_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);

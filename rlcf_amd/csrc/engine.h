@@ -241,6 +241,10 @@ struct rlcf_engine {
     DevBuf loss_ws;                  // double scratch of the distillation / TPT loss kernels (one per row, kd_split_ws_bytes, tpt_ws_bytes)
     DevBuf kd_teacher;               // [n_sel, C] the reward model's logits of the selected views (distillation losses, step 0 on)
     int kd_teacher_rows = 0, kd_teacher_C = 0;   // what kd_teacher holds: rows x bank size of the last distillation call (0 after a new bank)
+    // CoCoOp (TPT/clip/cocoop.py): the student's meta-net Linear(D, H) -> ReLU -> Linear(H, Wt) (rlcf_engine_set_meta_net; mn_H = 0: none),
+    // the un-normalised image features of the last generator pass [max_views, D] and the prompt it generated [n_ctx, Wt]
+    DevBuf mn_w1, mn_b1, mn_w2, mn_b2, cocoop_raw, cocoop_ctx;
+    int mn_H = 0;
     DevBuf step_skip;                // int32 per test sample: gradient held an inf / NaN -> optimizer step skipped (GradScaler semantics)
     // packed class-sequence runs of the text pass being enqueued (set by text_forward around transformer_forward)
     const rlcf_seq* pk_cur = nullptr; int n_pk_cur = 0; const int32_t* rss_cur = nullptr;
@@ -277,7 +281,7 @@ static inline bool prec_x3(const rlcf_engine* e) { return e->precision == RLCF_P
 static inline bool prec_single(const rlcf_engine* e) { return e->precision == RLCF_PREC_F16; }
 // resnet.hip
 int resnet_finalize(rlcf_engine* e, ClipModel& m, hipStream_t st);
-int resnet_encode(rlcf_engine* e, ClipModel& m, const float* images, int n, float* feats, hipStream_t st);
+int resnet_encode(rlcf_engine* e, ClipModel& m, const float* images, int n, float* feats, hipStream_t st, float* raw_out = nullptr);
 // norm-layer tuning of a ResNet student (resnet.hip): build the train-form weights / flat buffers once; one tuning sample
 int engine_gemm_conv3x3(rlcf_engine* e, const float* in, const float* scale2_dev, const float* W, const float* bias, const float* res, int ldr,
                         float* C, int ldc, int n, int H, int Wd, int cin, int cout, int epi, hipStream_t st, float* amax_out,
@@ -305,11 +309,18 @@ int engine_make_split(rlcf_engine* e, ClipModel& m, const float* w, size_t numel
 int engine_finalize(rlcf_engine* e, int which, hipStream_t st);
 int engine_set_class_bank(rlcf_engine* e, const int32_t* tokens, int C, int n_ctx, const float* ctx_init, int text_mode, hipStream_t st,
                           const int32_t* student_tokens = nullptr, const int32_t* ctx_pos = nullptr);
-int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, float* feats, hipStream_t st, int in_res = 0);
+// raw_out (optional, [n, D]): the features before the L2 normalisation as well (what CoCoOp's meta-net reads, cocoop.py:175-180)
+int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, float* feats, hipStream_t st, int in_res = 0, float* raw_out = nullptr);
 int engine_text_features(rlcf_engine* e, int which, const float* ctx, float* txt, hipStream_t st);
 int engine_logits(rlcf_engine* e, const float* img, int n, const float* txt, int C, float* logits, hipStream_t st);
 int engine_text_backward_dense(rlcf_engine* e, const float* ctx, const float* img, int n, const float* dlogits, float* dctx, hipStream_t st);
 int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
+// CoCoOp (engine_prompt.inl): the meta-net, the generator pass, the prompt step from given features, the fused per-image call
+int engine_set_meta_net(rlcf_engine* e, const float* w1, const float* b1, const float* w2, const float* b2, int H, hipStream_t st);
+int engine_cocoop_gen_ctx(rlcf_engine* e, const float* views, int N, int aug, float* feats_raw_out, float* ctx_out, hipStream_t st);
+int engine_tta_sample_feats(rlcf_engine* e, const float* feats_raw, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
+int engine_tta_sample_cocoop(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, float* feats_raw_out,
+                             float* ctx_gen_out, hipStream_t st);
 int engine_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
 int engine_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
 int engine_visual_enable(rlcf_engine* e, hipStream_t st);

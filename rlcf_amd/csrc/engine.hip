@@ -1032,7 +1032,7 @@ static int transformer_backward(rlcf_engine* e, const TowerW& w, Tower& ws, cons
 // ------------------------------------------------------------------ image tower
 // VisionTransformer.forward (TPT/clip/model.py:223-240) + L2 normalise (custom_clip.py:330,
 // clip_reward.py:136).  Runs under no_grad in the reference (custom_clip.py:325-327).
-int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, float* feats, hipStream_t st, int in_res) {
+int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, float* feats, hipStream_t st, int in_res, float* raw_out) {
     ClipModel& m = e->model[which];
     if (!m.finalized) { rlcf_set_error("model %d not finalized", which); return RLCF_ERR_STATE; }
     RLCF_ARG_CHECK(n > 0 && n <= e->max_views);
@@ -1043,7 +1043,7 @@ int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, f
         TRY(launch_bicubic(images, IMG_BUF(e, resized).as<float>(), n * 3, in_res, c.image_resolution, st));
         images = IMG_BUF(e, resized).as<float>();
     }
-    if (is_resnet(c)) return resnet_encode(e, m, images, n, feats, st);
+    if (is_resnet(c)) return resnet_encode(e, m, images, n, feats, st, raw_out);
     const int Wv = c.vision_width, tok = m.tokens, G2 = tok - 1, T = n * tok, D = c.embed_dim;
     if (e->ws_sel) {               // side-stream scratch grows on demand (first call of a size only)
         auto& sb = e->side_img;
@@ -1089,6 +1089,7 @@ int engine_encode_image(rlcf_engine* e, int which, const float* images, int n, f
     TRY(gemm(e, IMG_BUF(e, cls_ln).as<float>(), Wv, m.vprojT, Wv, nullptr, nullptr, 0, nullptr, 0, IMG_BUF(e, feat_raw).as<float>(), D, n, D, Wv, 1.f,
              RLCF_EPI_NONE, st));
     TRY(launch_l2norm_rows(IMG_BUF(e, feat_raw).as<float>(), feats, nullptr, n, D, st));
+    if (raw_out) RLCF_HIP_CHECK(hipMemcpyAsync(raw_out, IMG_BUF(e, feat_raw).p, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RLCF_OK;
 }
 

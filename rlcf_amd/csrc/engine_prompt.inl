@@ -211,8 +211,13 @@ static int optim_step(rlcf_engine* e, const rlcf_tta_args* a, int j, const Optim
     return RLCF_OK;
 }
 
-// Harness body TPT/tpt_cls_rl.py:251-262 around test_time_tuning (:47-79).
-int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
+// Harness body TPT/tpt_cls_rl.py:251-262 around test_time_tuning (:47-79).  What feeds the step its image features:
+//   views != NULL       the student image tower runs over them (rlcf_tta_sample)
+//   feats_raw != NULL   the caller's un-normalised features [N, D] are L2-normalised (rlcf_tta_sample_feats; TPT/clip/cocoop.py:208)
+//   both NULL           e->img_feat already holds the normalised features of this sample (rlcf_tta_sample_cocoop: the generator's pass)
+// Without views there is nothing for a reward model to read: the entries allow those two forms with the TPT loss alone.
+static int tta_sample_core(rlcf_engine* e, const float* views, const float* feats_raw, int N, const rlcf_tta_args* a, const rlcf_tta_out* out,
+                           hipStream_t st) {
     ClipModel& s = e->model[RLCF_STUDENT];
     RLCF_ARG_CHECK(a && N > 0 && N <= e->max_views && a->tta_steps >= 0);
     const LossKind kind = loss_kind(a);
@@ -241,7 +246,8 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
     RLCF_HIP_CHECK(hipMemsetAsync(e->adam_m.p, 0, cb, st));
     RLCF_HIP_CHECK(hipMemsetAsync(e->adam_v.p, 0, cb, st));
     // student image features of all N views: computed once (the image tower is frozen, custom_clip.py:325-327)
-    TRY(engine_encode_image(e, RLCF_STUDENT, views, N, e->img_feat.as<float>(), st));
+    if (views) TRY(engine_encode_image(e, RLCF_STUDENT, views, N, e->img_feat.as<float>(), st));
+    else if (feats_raw) TRY(launch_l2norm_rows(feats_raw, e->img_feat.as<float>(), nullptr, N, D, st));
     TextPassIO io = full_io(e, e->lay[0]);
     static int no_overlap = -1;                              // RLCF_NO_OVERLAP=1: everything on the caller's stream (benchmarks)
     if (no_overlap < 0) { const char* ev = getenv("RLCF_NO_OVERLAP"); no_overlap = ev ? atoi(ev) : 0; }
@@ -259,7 +265,7 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
             TRY(engine_logits(e, e->img_feat.as<float>(), N, txt_j, C, e->logits.as<float>(), st));
             TRY(launch_entropy_select(e->logits.as<float>(), N, C, n_sel, e->entropy.as<float>(), e->sel_idx.as<int32_t>(), st));
             TRY(launch_gather_rows(e->img_feat.as<float>(), D, e->sel_idx.as<int32_t>(), e->sel_feat.as<float>(), D, n_sel, D, st));
-            TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
+            if (views) TRY(launch_gather_rows(views, (int)img_elems, e->sel_idx.as<int32_t>(), e->views_sel.as<float>(), (int)img_elems, n_sel, (int)img_elems, st));
             // the reward models' pass over the selected views depends on nothing the student does from here to the loss, and at one
             // image's sizes neither it nor the sparse text forward fills the chip: second stream, joined before the loss kernel
             if (overlap) {
@@ -331,6 +337,65 @@ int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_
     COPY_OUT(out->final_logits, e->final_logits.p, (size_t)C * sizeof(float));
     COPY_OUT(out->top5, e->top5.p, 5 * sizeof(int32_t));
     return RLCF_OK;
+}
+int engine_tta_sample(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
+    return tta_sample_core(e, views, nullptr, N, a, out, st);
+}
+
+// ------------------------------------------------------------------ CoCoOp (TPT/clip/cocoop.py, the --cocoop branch of TPT/tpt_cls.py)
+// The generator's ctx parameter is the class bank's ctx_init (cocoop.py:51); the meta-net is the student's (:52-56).
+int engine_set_meta_net(rlcf_engine* e, const float* w1, const float* b1, const float* w2, const float* b2, int H, hipStream_t st) {
+    const rlcf_clip_cfg& c = e->model[RLCF_STUDENT].cfg;
+    const size_t D = (size_t)c.embed_dim, W = (size_t)c.text_width, h = (size_t)H;
+    TRY(e->mn_w1.ensure(h * D * sizeof(float))); TRY(e->mn_b1.ensure(h * sizeof(float)));
+    TRY(e->mn_w2.ensure(W * h * sizeof(float))); TRY(e->mn_b2.ensure(W * sizeof(float)));
+    RLCF_HIP_CHECK(hipMemcpyAsync(e->mn_w1.p, w1, h * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    RLCF_HIP_CHECK(hipMemcpyAsync(e->mn_b1.p, b1, h * sizeof(float), hipMemcpyDeviceToDevice, st));
+    RLCF_HIP_CHECK(hipMemcpyAsync(e->mn_w2.p, w2, W * h * sizeof(float), hipMemcpyDeviceToDevice, st));
+    RLCF_HIP_CHECK(hipMemcpyAsync(e->mn_b2.p, b2, W * sizeof(float), hipMemcpyDeviceToDevice, st));
+    e->mn_H = H;
+    return RLCF_OK;
+}
+// what a generator pass needs of the engine: a meta-net and a class bank with learnable context rows
+static int cocoop_state_check(const rlcf_engine* e, const char* entry) {
+    if (e->mn_H <= 0) { rlcf_set_error("%s: no meta-net set (rlcf_engine_set_meta_net)", entry); return RLCF_ERR_STATE; }
+    if (e->C <= 0 || e->image_bank || e->n_ctx <= 0) {
+        rlcf_set_error("%s: needs a class bank with learnable context rows (rlcf_engine_set_class_bank, n_ctx > 0): its ctx_init is the generator's ctx", entry);
+        return RLCF_ERR_STATE;
+    }
+    return RLCF_OK;
+}
+// CoCoOpCLIP.gen_ctx (cocoop.py:172-182): one student image pass; the meta-net reads the UN-normalised features — row 0 (aug) or the
+// mean over the rows.  The normalised features stay in e->img_feat, the raw ones in e->cocoop_raw, the prompt in e->cocoop_ctx.
+int engine_cocoop_gen_ctx(rlcf_engine* e, const float* views, int N, int aug, float* feats_raw_out, float* ctx_out, hipStream_t st) {
+    TRY(cocoop_state_check(e, "rlcf_cocoop_gen_ctx"));
+    ClipModel& s = e->model[RLCF_STUDENT];
+    RLCF_ARG_CHECK(N > 0 && N <= e->max_views);
+    const int D = s.cfg.embed_dim, Wt = s.cfg.text_width, n_ctx = e->n_ctx;
+    TRY(e->cocoop_raw.ensure((size_t)e->max_views * D * sizeof(float)));
+    TRY(e->cocoop_ctx.ensure((size_t)n_ctx * Wt * sizeof(float)));
+    float* raw = e->cocoop_raw.as<float>();
+    TRY(engine_encode_image(e, RLCF_STUDENT, views, N, e->img_feat.as<float>(), st, 0, raw));
+    TRY(launch_cocoop_ctx(raw, D, aug ? 1 : N, aug ? 0 : 1, e->ctx_init.as<float>(), n_ctx, e->mn_w1.as<float>(), e->mn_b1.as<float>(),
+                          e->mn_w2.as<float>(), e->mn_b2.as<float>(), D, e->mn_H, Wt, e->cocoop_ctx.as<float>(), st));
+    COPY_OUT(feats_raw_out, raw, (size_t)N * D * sizeof(float));
+    COPY_OUT(ctx_out, e->cocoop_ctx.p, (size_t)n_ctx * Wt * sizeof(float));
+    return RLCF_OK;
+}
+// test_time_tuning on (image_feature, pgen_ctx) + the final call (TPT/tpt_cls.py:49-78,285-295): the prompt step from given features
+int engine_tta_sample_feats(rlcf_engine* e, const float* feats_raw, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st) {
+    return tta_sample_core(e, nullptr, feats_raw, N, a, out, st);
+}
+// The loop body TPT/tpt_cls.py:280-297 with args.cocoop and args.tpt: gen_ctx(aug = True), the step, the final logits — one image
+// pass.  The step is tta_sample_core on the features the generator's pass left in e->img_feat: the kernels, shapes and order of
+// rlcf_cocoop_gen_ctx followed by rlcf_tta_sample_feats (whose L2 normalisation of the raw rows is the image pass's own kernel on the
+// same rows), so the two forms give the same bits.
+int engine_tta_sample_cocoop(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, float* feats_raw_out,
+                             float* ctx_gen_out, hipStream_t st) {
+    TRY(engine_cocoop_gen_ctx(e, views, N, 1, feats_raw_out, ctx_gen_out, st));
+    rlcf_tta_args b = *a;
+    b.ctx_in = e->cocoop_ctx.as<float>();
+    return tta_sample_core(e, nullptr, nullptr, N, &b, out, st);
 }
 
 // ------------------------------------------------------------------ B test samples per pass

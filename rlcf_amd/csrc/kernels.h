@@ -148,6 +148,10 @@ int launch_kd_loss_split(const float* student, int ld_s, const float* teacher, i
 // optional (one at least); ws = caller-owned scratch of tpt_ws_bytes(groups, n, C) bytes
 size_t tpt_ws_bytes(int groups, int n, int C);
 int launch_tpt_loss(const float* logits, int ld, int groups, int n, int C, float* loss, float* dlogits, double* ws, hipStream_t st);
+// the CoCoOp prompt generator (cocoop.hip): out [mean ? 1 : n, n_ctx, W] = ctx + (W2 relu(W1 f + b1) + b2) per feature row f, or for the
+// mean of the n rows; w1 [H, D], b1 [H], w2 [W, H], b2 [W] (nn.Linear layout), feats [n, D] with row stride ld
+int launch_cocoop_ctx(const float* feats, int ld, int n, int mean, const float* ctx, int n_ctx, const float* w1, const float* b1,
+                      const float* w2, const float* b2, int D, int H, int W, float* out, hipStream_t st);
 // recall ranks of score rows (kd.hip): gt_off = CSR offsets [rows + 1] or NULL (one ground-truth index per row)
 int launch_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_off, const int32_t* gt_idx, int32_t* ranks,
                            hipStream_t st);

@@ -433,7 +433,7 @@ static int avgpool2(const float* in, float* out, int n, int Ho, int Wo, int C, h
 }
 
 // ModifiedResNet.forward (model.py:138-154) + L2 normalisation of the features (custom_clip.py:330, clip_reward.py:136)
-int resnet_encode(rlcf_engine* e, ClipModel& m, const float* images, int n_total, float* feats, hipStream_t st) {
+int resnet_encode(rlcf_engine* e, ClipModel& m, const float* images, int n_total, float* feats, hipStream_t st, float* raw_out) {
     const rlcf_clip_cfg& c = m.cfg;
     const ResNetW& r = m.rn;
     const int R = c.image_resolution, w = c.vision_width, E = r.E, D = c.embed_dim, HW = r.out_hw * r.out_hw, T = HW + 1;
@@ -534,6 +534,7 @@ int resnet_encode(rlcf_engine* e, ClipModel& m, const float* images, int n_total
         RLCF_LAUNCH_CHECK();
         TRY(engine_gemm(e, e->rn_att.as<float>(), E, r.c_w, E, r.c_b, nullptr, 0, e->feat_raw.as<float>(), D, n, D, E, RLCF_EPI_NONE, st));
         TRY(launch_l2norm_rows(e->feat_raw.as<float>(), feats + (size_t)i0 * D, nullptr, n, D, st));
+        if (raw_out) RLCF_HIP_CHECK(hipMemcpyAsync(raw_out + (size_t)i0 * D, e->feat_raw.p, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return RLCF_OK;
 }

@@ -116,6 +116,30 @@ def tpt_loss_op(logits: torch.Tensor, groups: int = 1, want_loss: bool = True, w
     return loss, dlogits
 
 
+def cocoop_ctx_op(feats: torch.Tensor, ctx: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                  mean: bool = False) -> torch.Tensor:
+    """One rlcf_cocoop_ctx launch: ctx + meta_net(f) per feature row of `feats` [n, D] (any row stride) -> [n, n_ctx, W], or for the
+    mean of the rows -> [1, n_ctx, W].  w1 [H, D], b1 [H], w2 [W, H], b2 [W]: the nn.Linear layout of cocoop.py:52-56."""
+    assert feats.dim() == 2 and feats.dtype == torch.float32 and feats.stride(1) == 1, "float32 rows, contiguous within a row"
+    n, Dn = feats.shape
+    dev = feats.device
+    ctx, w1, b1, w2, b2 = [t.detach().to(dev, torch.float32).contiguous() for t in (ctx, w1, b1, w2, b2)]
+    H, (n_ctx, W) = w1.shape[0], ctx.shape
+    assert w1.shape == (H, Dn) and b1.shape == (H,) and w2.shape == (W, H) and b2.shape == (W,)
+    out = torch.empty(1 if mean else n, n_ctx, W, device=dev)
+    L.check(L.lib().rlcf_cocoop_ctx(feats.data_ptr(), feats.stride(0), n, 1 if mean else 0, _ptr(ctx), n_ctx, _ptr(w1), _ptr(b1), _ptr(w2),
+                                    _ptr(b2), Dn, H, W, _ptr(out), _stream()), "cocoop_ctx")
+    return out
+
+
+def l2norm_rows(x: torch.Tensor) -> torch.Tensor:
+    """rlcf_l2norm_rows: x / |x| per row of float32 device rows [n, D] (the engine's own normalisation kernel)"""
+    x = x.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(x)
+    L.check(L.lib().rlcf_l2norm_rows(_ptr(x), _ptr(out), x.shape[0], x.shape[1], _stream()), "l2norm_rows")
+    return out
+
+
 def kd_loss_split_op(student: torch.Tensor, teacher: torch.Tensor, params: Optional[L.KdParams] = None, row_loss: bool = False):
     """One rlcf_kd_loss_split call (kd_distill_loss_v2 on few, long rows; any row stride): (loss [1], dlogits [n, C], row losses or None)."""
     assert student.dim() == 2 and student.shape == teacher.shape and student.dtype == teacher.dtype == torch.float32
@@ -275,6 +299,58 @@ class Engine:
             parts = torch.split(o["reward_image_features"].view(-1), [n_sel * r.embed_dim for r in self.rewards])
             parts = [p.view(n_sel, r.embed_dim) for p, r in zip(parts, self.rewards)]
             o["reward_image_features"] = parts[0] if len(parts) == 1 else parts
+        return o
+
+    # ---- CoCoOp (TPT/clip/cocoop.py; the --cocoop branch of TPT/tpt_cls.py) -------------------------------------------
+    def set_meta_net(self, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> None:
+        """the student's meta-net Linear(D, H) -> ReLU -> Linear(H, W) in nn.Linear layout (rlcf_engine_set_meta_net); the
+        generator's ctx is the class bank's ctx_init"""
+        t = [x.detach().to(self.device, torch.float32).contiguous() for x in (w1, b1, w2, b2)]
+        H = int(t[0].shape[0])
+        assert t[0].shape == (H, self.student.embed_dim) and t[1].shape == (H,), "linear1: [H, embed_dim], [H]"
+        assert t[2].shape == (self.student.transformer_width, H) and t[3].shape == (self.student.transformer_width,), "linear2: [W, H], [W]"
+        L.check(self.lib.rlcf_engine_set_meta_net(self.h, *[_ptr(x) for x in t], H, _stream()), "set_meta_net")
+
+    def cocoop_gen_ctx(self, views: torch.Tensor, aug: bool = False):
+        """CoCoOpCLIP.gen_ctx (cocoop.py:172-182) -> (un-normalised image features [N, D], generated prompt [n_ctx, W])"""
+        views = views.to(self.device, torch.float32).contiguous()
+        N = views.shape[0]
+        feats = torch.empty(N, self.student.embed_dim, device=self.device)
+        ctx = torch.empty(self.n_ctx, self.student.transformer_width, device=self.device)
+        L.check(self.lib.rlcf_cocoop_gen_ctx(self.h, _ptr(views), N, 1 if aug else 0, _ptr(feats), _ptr(ctx), _stream()), "cocoop_gen_ctx")
+        return feats, ctx
+
+    _COCOOP_FIELDS = ("logits", "entropy", "selected_idx", "loss", "dlogits", "ctx_grad")
+
+    def _cocoop_outputs(self, cfg: TTAConfig, N: int, want_intermediates: bool, skip_final: bool):
+        fields = ["ctx_after", "step_skipped"] + ([] if skip_final else ["final_logits", "top5"])
+        if want_intermediates and cfg.tta_steps > 0:
+            fields += list(self._COCOOP_FIELDS)
+        o = self._outputs(fields, cfg, N, cfg.n_sel(N))
+        return o, L.TTAOut(**{k: _ptr(o[k]) if k in o else None for k in L.TTA_OUT_FIELDS})
+
+    def tta_sample_feats(self, feats_raw: torch.Tensor, ctx_in: torch.Tensor, cfg: TTAConfig, want_intermediates: bool = True,
+                         skip_final: bool = False) -> Dict[str, torch.Tensor]:
+        """the prompt step from given un-normalised features and a starting prompt (rlcf_tta_sample_feats; cfg.tpt only)"""
+        feats_raw = feats_raw.detach().to(self.device, torch.float32).contiguous()
+        ctx_in = ctx_in.detach().to(self.device, torch.float32).contiguous()
+        N = feats_raw.shape[0]
+        o, co = self._cocoop_outputs(cfg, N, want_intermediates, skip_final)
+        a = cfg.c_args(N, skip_final, ctx_in)
+        L.check(self.lib.rlcf_tta_sample_feats(self.h, _ptr(feats_raw), N, C.byref(a), C.byref(co), _stream()), "tta_sample_feats")
+        return o
+
+    def tta_sample_cocoop(self, views: torch.Tensor, cfg: TTAConfig, want_intermediates: bool = True) -> Dict[str, torch.Tensor]:
+        """the loop body TPT/tpt_cls.py:280-297 with --cocoop --tpt as one call (rlcf_tta_sample_cocoop): the outputs of the step
+        plus image_features [N, D] (un-normalised) and ctx_gen [n_ctx, W]"""
+        views = views.to(self.device, torch.float32).contiguous()
+        N = views.shape[0]
+        o, co = self._cocoop_outputs(cfg, N, want_intermediates, False)
+        o["image_features"] = torch.empty(N, self.student.embed_dim, device=self.device)
+        o["ctx_gen"] = torch.empty(self.n_ctx, self.student.transformer_width, device=self.device)
+        a = cfg.c_args(N)
+        L.check(self.lib.rlcf_tta_sample_cocoop(self.h, _ptr(views), N, C.byref(a), C.byref(co), _ptr(o["image_features"]), _ptr(o["ctx_gen"]),
+                                                _stream()), "tta_sample_cocoop")
         return o
 
     def ln_params(self, pristine: bool = False) -> torch.Tensor:

@@ -1,6 +1,6 @@
 """Flags of the RLCF classification entry points: same names, types and defaults as the reference (TPT/params.py:13-98), so the command
-lines of TPT/scripts/*.sh parse identically.  Flags the HIP path has no use for (--workers, --dataset_mode, --cocoop, --corruption,
---level, --confidence_gap*) are accepted and ignored; --hard_aug 1 selects the BYOL-style recipe of the view pipeline (datautils.HardAugParams);
+lines of TPT/scripts/*.sh parse identically.  Flags the HIP path has no use for (--workers, --dataset_mode, --corruption,
+--level, --confidence_gap*) are accepted and ignored; --cocoop / --load are read by rlcf_amd.tpt_cls (TPT/tpt_cls.py:100-103); --hard_aug 1 selects the BYOL-style recipe of the view pipeline (datautils.HardAugParams);
 --kd_loss (KD / DKD / ATKD) is read by the distillation entry rlcf_amd.tune_cls_kd (TPT/tune_cls_kd.py, scripts/kd-tune.sh) and by
 nothing else."""
 import argparse
@@ -27,8 +27,10 @@ def get_args(argv=None):
     p.add_argument("--tta_steps", default=1, type=int)
     p.add_argument("--n_ctx", default=4, type=int)
     p.add_argument("--ctx_init", default=None, type=str)
-    p.add_argument("--cocoop", action="store_true", default=False, help="accepted for script compatibility (CoCoOp initialisation is not on the RLCF path)")
-    p.add_argument("--load", default=None, type=none_or_str)
+    p.add_argument("--cocoop", action="store_true", default=False, help="TPT/tpt_cls.py only: CoCoOp prompts (a model from rlcf_amd.cocoop.get_cocoop with --load's weights, tta_steps 0 or 1); the RLCF entries ignore it")
+    p.add_argument("--load", default=None, type=none_or_str,
+                   help="checkpoint with a pre-trained prompt: {'state_dict': {'ctx': ...}} (CoOp, tpt_cls_rl.py:95-101) or, with --cocoop, ctx and the meta-net "
+                        "(rlcf_amd.cocoop.load_cocoop_weights)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--output", type=str, default="exp_01")
     p.add_argument("--dataset_mode", type=str, default="test", help="accepted (the HIP path ships a synthetic stream only)")

@@ -35,6 +35,9 @@ class Session:
         self.image_bank = None       # (student features [n, D], [reward features [n, Dr]]): the bank of the text -> image retrieval direction
         self._bank_version = 0       # bumped by set_bank: the engine re-reads the class bank when its copy is older
         self._bank_applied = -1
+        self.meta_net = None         # CoCoOp: (w1, b1, w2, b2) of the student's meta-net (rlcf_amd.cocoop), re-applied whenever the engine is rebuilt
+        self._meta_version = 0
+        self._meta_applied = -1
         self.bn_prior_strength = -1  # `--prior_strength` (ResNet students, tune_cls_rl.py:73-76): re-applied whenever the engine is rebuilt
 
     def set_student(self, ckpt):
@@ -61,6 +64,11 @@ class Session:
         self.image_bank = None
         self._bank_version += 1
 
+    def set_meta_net(self, w1, b1, w2, b2):
+        """CoCoOp's meta-net (TPT/clip/cocoop.py:52-56) in nn.Linear layout; the generator's ctx travels as the class bank's ctx_init"""
+        self.meta_net = tuple(t.detach().clone() for t in (w1, b1, w2, b2))
+        self._meta_version += 1
+
     def set_image_bank(self, student_feats: torch.Tensor, reward_feats):
         """text -> image retrieval: a bank of image features replaces the class / caption bank"""
         rf = list(reward_feats) if isinstance(reward_feats, (list, tuple)) else [reward_feats]
@@ -79,11 +87,14 @@ class Session:
             if self._engine is not None:
                 self._engine.close()
             self._close_lanes()
-            self._engine, self._key, self._bank_applied = self._build(n_cls), key, None
+            self._engine, self._key, self._bank_applied, self._meta_applied = self._build(n_cls), key, None, -1
         bkey = self._bank_key()
         if bkey is not None and bkey != self._bank_applied:
             self._apply_bank(self._engine)
             self._bank_applied = bkey
+        if self.meta_net is not None and self._meta_applied != self._meta_version:
+            self._engine.set_meta_net(*self.meta_net)
+            self._meta_applied = self._meta_version
         return self._engine
 
     def _build(self, n_cls: int) -> Engine:
@@ -142,6 +153,7 @@ class Session:
         self._close_lanes()
         self._engine = None
         self._key = self._bank_applied = None
+        self._meta_applied = -1
 
 
 SESSION = Session()

@@ -463,3 +463,18 @@ def reward_members(spec: str, seeds, device=None) -> list:
     seeds = [int(x) for x in seeds.split("+")] if isinstance(seeds, str) else list(seeds)
     kw = {} if device is None else {"device": device}
     return [(GEOMETRIES[n], make_state_dict(GEOMETRIES[n], seed=s, **kw)) for n, s in zip(names, seeds)]
+
+
+def make_cocoop_state(geo: ClipGeometry, seed: int, n_ctx: int = 4, shift_std: float = 0.02) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained CoCoOp checkpoint (TPT/clip/cocoop.py:51-56) in the key layout of CoCoOpPromptLearner.state_dict():
+    `ctx` [n_ctx, W] and the meta-net Linear(D, D // 16) -> ReLU -> Linear(D // 16, W).  Scaled so that the meta-net matters: linear1
+    keeps un-normalised image features (|f| ~ sqrt(D) on these synthetic towers) at O(1) pre-activations of both signs, linear2 turns
+    them into a shift of about `shift_std` per element — the size of a token embedding, i.e. of ctx itself."""
+    D, W, H = geo.embed_dim, geo.transformer_width, geo.embed_dim // 16
+    return {
+        "ctx": normal(seed, "cocoop.ctx", (n_ctx, W), 0.02),
+        "meta_net.linear1.weight": normal(seed, "cocoop.w1", (H, D), D ** -0.5),
+        "meta_net.linear1.bias": normal(seed, "cocoop.b1", (H,), 0.25),
+        "meta_net.linear2.weight": normal(seed, "cocoop.w2", (W, H), shift_std * H ** -0.5),
+        "meta_net.linear2.bias": normal(seed, "cocoop.b2", (W,), 0.25 * shift_std),
+    }
