@@ -453,6 +453,38 @@ int rlcf_tta_sample_feats(rlcf_engine*, const float* feats_raw, int N, const rlc
                           rlcf_stream stream);
 int rlcf_tta_sample_cocoop(rlcf_engine*, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out,
                            float* feats_raw_out, float* ctx_gen_out, rlcf_stream stream);
+/* (ABI version 20) Zero-shot evaluation, TPT/zero_shot.py, and the ensemble classifier CLIPCLS_TTA_Multiple
+ * (TPT/clip/custom_clip.py:500-583).
+ * rlcf_ensemble_logits — CLIPCLS_TTA_Multiple.forward's mixing (custom_clip.py:555-566), stateless:
+ *   logits[b, c] = (1 / M) sum_{m < M} scale_m <img_m[b, :D_m], txt_m[c, :D_m]>: per model `logit_scale.exp() * img @ txt.t()`, then
+ *   torch.mean(torch.stack(...)); M = 1 is CLIPCLS_TTA.forward (:423-432).  The descriptor is a HOST struct passed to the kernel by
+ *   value (no device-side pointer table, no staging): per model the DEVICE rows img [n, D] (row stride ld_img) and txt [C, D] (row stride
+ *   ld_txt), already L2-normalised (the kernel does not normalise), and scale = exp(logit_scale).  One launch for all models; sums in
+ *   double (dot products, scale, the sum over the models in model order, 1 / M), rounded to float once; no atomics: two calls give the
+ *   same bits and a row gives the same bits alone as inside a batch.  RLCF_ERR_ARG unless 1 <= M <= RLCF_ENS_MAX_MODELS, n >= 1, C >= 1,
+ *   D_m >= 4 and D_m % 4 == 0, both strides >= D_m and multiples of 4, ld_logits >= C, img / txt non-NULL and 16-byte aligned, and
+ *   n <= 16 * 65535.
+ * rlcf_zero_shot_batch — one batch of the loop TPT/zero_shot.py:139-161 as ONE call: images [n, 3, in_res, in_res] are n DIFFERENT test
+ *   images (n <= max_views).  ensemble = 0: the student alone (CLIPCLS_TTA.forward); ensemble != 0: the student and every further slot
+ *   of an engine made by rlcf_engine_create_ensemble, in the order student, slot 0, slot 1, ... (CLIPCLS_TTA_Multiple.forward).  A model
+ *   whose input resolution differs from in_res gets the bicubic align_corners=True resample, the student too (custom_clip.py:541-544).
+ *   The student's class features are the text features of the class bank at ctx_init (get_class_features, :405-409 / :526-534), the
+ *   further models' the cached reward class banks.  Then one rlcf_ensemble_logits launch, the rows' top-5 (ties to the lower index)
+ *   and, with target (DEVICE int64 [n]), hits[0] += #(target == top5[:, 0]), hits[1] += #(target in top5) as rlcf_top5_hits counts
+ *   them: hits (DEVICE float[2]) ACCUMULATES, a dataset loop reads it back once (accuracy weighted by batch size, zero_shot.py:159-161,
+ *   is 100 hits / images).  logits [n, C] and top5 [n, 5] optional.  No host synchronisation.  The student runs with its current
+ *   LayerNorm / visual state; the call writes scratch of its own only, so a following rlcf_tta_* call computes what it would have
+ *   computed without it.  RLCF_ERR_ARG: n < 1 or n > max_views, in_res < 1, target without hits (or hits without target);
+ *   RLCF_ERR_STATE: no class bank, ensemble != 0 on an engine without a further model.
+ * rlcf_engine_logit_scale_exp — exp(logit_scale) of model `which` as the engine holds it after rlcf_engine_finalize (the float a
+ *   caller of rlcf_ensemble_logits passes to reproduce rlcf_zero_shot_batch bit for bit); 0 for a model that is absent or not finalized. */
+#define RLCF_ENS_MAX_MODELS 5
+typedef struct { const float* img; int ld_img; const float* txt; int ld_txt; int D; float scale; } rlcf_ens_model;
+typedef struct { int M; rlcf_ens_model m[RLCF_ENS_MAX_MODELS]; } rlcf_ens_desc;
+int rlcf_ensemble_logits(const rlcf_ens_desc* desc, int n, int C, float* logits, int ld_logits, rlcf_stream stream);
+float rlcf_engine_logit_scale_exp(rlcf_engine*, int which);
+int rlcf_zero_shot_batch(rlcf_engine*, const float* images, int n, int in_res, int ensemble, const int64_t* target, float* logits,
+                         int32_t* top5, float* hits, rlcf_stream stream);
 /* LayerNorm-tuning variant (TPT/tune_cls_rl.py with CLIPCLS_TTA(only_visual=True, only_norm=True),
  * custom_clip.py:364-497): the class text features are cached, the IMAGE encoder runs with grad and the tunable set is
  * every visual LayerNorm weight/bias, laid out [ln_pre.w, ln_pre.b, (ln_1.w, ln_1.b, ln_2.w, ln_2.b) x layers, ln_post.w,

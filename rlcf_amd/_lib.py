@@ -60,6 +60,17 @@ class KdParams(C.Structure):   # rlcf_kd_params: hyper-parameters of the three d
     _fields_ = [(n, C.c_float) for n in ("T_stu", "T_tea", "alpha", "beta", "temperature", "multiplier", "eps")]
 
 
+ENS_MAX_MODELS = 5
+
+
+class EnsModel(C.Structure):   # rlcf_ens_model: one model of rlcf_ensemble_logits (device rows, strides in floats, exp(logit_scale))
+    _fields_ = [("img", C.c_void_p), ("ld_img", C.c_int), ("txt", C.c_void_p), ("ld_txt", C.c_int), ("D", C.c_int), ("scale", C.c_float)]
+
+
+class EnsDesc(C.Structure):    # rlcf_ens_desc: passed to the kernel by value
+    _fields_ = [("M", C.c_int), ("m", EnsModel * ENS_MAX_MODELS)]
+
+
 TTA_OUT_FIELDS = ("logits", "entropy", "selected_idx", "topk_idx", "clip_score", "rewards", "loss", "dlogits",
                   "ctx_grad", "ctx_after", "reward_image_features", "final_logits", "top5", "ln_grad", "ln_after", "vis_grad", "vis_after", "step_skipped")
 
@@ -132,6 +143,9 @@ SIGNATURES = {
     "rlcf_cocoop_gen_ctx": (I, [P, P, I, I, P, P, P]),
     "rlcf_tta_sample_feats": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
     "rlcf_tta_sample_cocoop": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P, P, P]),
+    "rlcf_ensemble_logits": (I, [C.POINTER(EnsDesc), I, I, P, I, P]),
+    "rlcf_engine_logit_scale_exp": (F, [P, I]),
+    "rlcf_zero_shot_batch": (I, [P, P, I, I, I, P, P, P, P, P]),
     "rlcf_tta_batch": (I, [P, P, I, I, C.POINTER(TTAArgs), P, P, P]),
     "rlcf_tta_sample_ln": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),
     "rlcf_tta_retrieval_image": (I, [P, P, I, C.POINTER(TTAArgs), C.POINTER(TTAOut), P]),

@@ -35,7 +35,7 @@ int rlcf_func_lds(const void* fn, size_t bytes) {
 extern "C" {
 
 const char* rlcf_last_error(void) { return g_err; }
-int rlcf_version(void) { return 19; }   // 19: CoCoOp (rlcf_cocoop_ctx, rlcf_l2norm_rows, rlcf_engine_set_meta_net, rlcf_cocoop_gen_ctx, rlcf_tta_sample_feats, rlcf_tta_sample_cocoop: the --cocoop branch of TPT/tpt_cls.py); 18: rlcf_gemm_f16x3_grid_w (the two-pass split-f16 product as a stand-alone call); 17: the TPT baseline (rlcf_tpt_loss, RLCF_F_TPT on rlcf_tta_sample / _sample_ln / _sample_visual / _batch / _batch_ln: avg_entropy in place of the reward loss, an engine without a reward model); 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
+int rlcf_version(void) { return 20; }   // 20: zero-shot evaluation (rlcf_ensemble_logits, rlcf_zero_shot_batch, rlcf_engine_logit_scale_exp: TPT/zero_shot.py and CLIPCLS_TTA_Multiple); 19: CoCoOp (rlcf_cocoop_ctx, rlcf_l2norm_rows, rlcf_engine_set_meta_net, rlcf_cocoop_gen_ctx, rlcf_tta_sample_feats, rlcf_tta_sample_cocoop: the --cocoop branch of TPT/tpt_cls.py); 18: rlcf_gemm_f16x3_grid_w (the two-pass split-f16 product as a stand-alone call); 17: the TPT baseline (rlcf_tpt_loss, RLCF_F_TPT on rlcf_tta_sample / _sample_ln / _sample_visual / _batch / _batch_ln: avg_entropy in place of the reward loss, an engine without a reward model); 16: retrieval distillation (rlcf_tta_retrieval_image_kd / _text_kd, rlcf_kd_loss_split, rlcf_engine_get_kd_teacher), rlcf_retrieval_ranks; 15: distillation losses (rlcf_kd_loss, RLCF_F_KD / DKD / ATKD on the image-encoder tuning calls); 14: samples in flight from one host thread (rlcf_lanes_*, rlcf_tta_lanes), rlcf_top5_hits; 13: rlcf_engine_set_side_stream (lane engines of samples in flight keep to the caller's stream); 12: rlcf_avg_entropy, rlcf_accuracy (the harness mirror's conveniences as kernels); 11: rlcf_engine_f16_grid_weights (two-pass products for weights on the fp16 grid); 10: rlcf_gemm_f16_ln / rlcf_ln_stats_final / rlcf_resid16_init (LayerNorm folded into the single-pass f16 products); 9: rlcf_gemm_f16 (single-pass f16 GEMM of the performance mode); 8: rlcf_make_views_hard (the hard_aug pre-augmentation); 7: every-parameter tuning of a ModifiedResNet student (rlcf_tta_sample_visual, rlcf_engine_encode_image_bn_form); 6: pair-operand attention, BatchNorm tuning of a ResNet student (rlcf_engine_*bn*), profile kinds 12 / 13; 5: text -> image retrieval; 4: rlcf_tta_args.n_sel, rlcf_tta_out.step_skipped, rlcf_engine_reset_visual_state, engine-owned scratch
 //    // 2: rlcf_clip_cfg.vision_stages, reward slots, views, LN batch; 3: rlcf_tta_out.vis_*, rlcf_tta_sample_visual
 
 // ------------------------------------------------------------------ op level
@@ -542,6 +542,24 @@ int rlcf_tta_sample_cocoop(rlcf_engine* e, const float* views, int N, const rlcf
     if (args->ctx_in) { rlcf_set_error("rlcf_tta_sample_cocoop: args->ctx_in must be NULL (the starting prompt is the one generated from views[0])"); return RLCF_ERR_ARG; }
     TTA_CHECK(e, args, "rlcf_tta_sample_cocoop", LOSS_BIT(LOSS_TPT), TTA_PROMPT);
     return engine_tta_sample_cocoop(e, views, N, args, out, feats_raw_out, ctx_gen_out, engine_stream(e, stream));
+}
+// ------------------------------------------------------------------ zero-shot evaluation (ABI 20)
+int rlcf_ensemble_logits(const rlcf_ens_desc* desc, int n, int C, float* logits, int ld_logits, rlcf_stream stream) {
+    return launch_ensemble_logits(desc, n, C, logits, ld_logits, (hipStream_t)stream);
+}
+float rlcf_engine_logit_scale_exp(rlcf_engine* e, int which) { return which_ok(e, which) && e->model[which].finalized ? e->model[which].logit_scale_exp : 0.f; }
+int rlcf_zero_shot_batch(rlcf_engine* e, const float* images, int n, int in_res, int ensemble, const int64_t* target, float* logits, int32_t* top5,
+                         float* hits, rlcf_stream stream) {
+    RLCF_ARG_CHECK(e && images);
+    if (n < 1 || n > e->max_views || in_res < 1) {
+        rlcf_set_error("rlcf_zero_shot_batch: n = %d images of resolution %d (need 1 <= n <= max_views = %d, in_res >= 1)", n, in_res, e->max_views);
+        return RLCF_ERR_ARG;
+    }
+    if ((target == nullptr) != (hits == nullptr)) {
+        rlcf_set_error("rlcf_zero_shot_batch: target and hits go together (the hit counts of `target` accumulate in `hits`; NULL both for logits / top-5 only)");
+        return RLCF_ERR_ARG;
+    }
+    return engine_zero_shot_batch(e, images, n, in_res, ensemble, target, logits, top5, hits, engine_stream(e, stream));
 }
 int rlcf_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* args, const rlcf_tta_out* out, rlcf_stream stream) {
     RLCF_ARG_CHECK(e && views && args);

@@ -245,6 +245,9 @@ struct rlcf_engine {
     // the un-normalised image features of the last generator pass [max_views, D] and the prompt it generated [n_ctx, Wt]
     DevBuf mn_w1, mn_b1, mn_w2, mn_b2, cocoop_raw, cocoop_ctx;
     int mn_H = 0;
+    // zero-shot evaluation (rlcf_zero_shot_batch): per model the normalised features of the batch [max_views, D_m], the mixed logits
+    // [max_views, C] and the rows' top-5 — the call's OWN scratch, so that it changes nothing a following rlcf_tta_* call reads
+    DevBuf zs_feat[1 + RLCF_MAX_REWARDS], zs_logits, zs_top5;
     DevBuf step_skip;                // int32 per test sample: gradient held an inf / NaN -> optimizer step skipped (GradScaler semantics)
     // packed class-sequence runs of the text pass being enqueued (set by text_forward around transformer_forward)
     const rlcf_seq* pk_cur = nullptr; int n_pk_cur = 0; const int32_t* rss_cur = nullptr;
@@ -321,6 +324,9 @@ int engine_cocoop_gen_ctx(rlcf_engine* e, const float* views, int N, int aug, fl
 int engine_tta_sample_feats(rlcf_engine* e, const float* feats_raw, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
 int engine_tta_sample_cocoop(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, float* feats_raw_out,
                              float* ctx_gen_out, hipStream_t st);
+// one batch of TPT/zero_shot.py:139-161 (engine_prompt.inl): towers, one ensemble-logits launch, top-5, hit counts
+int engine_zero_shot_batch(rlcf_engine* e, const float* images, int n, int in_res, int ensemble, const int64_t* target, float* logits,
+                           int32_t* top5, float* hits, hipStream_t st);
 int engine_tta_sample_ln(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
 int engine_tta_sample_visual(rlcf_engine* e, const float* views, int N, const rlcf_tta_args* a, const rlcf_tta_out* out, hipStream_t st);
 int engine_visual_enable(rlcf_engine* e, hipStream_t st);

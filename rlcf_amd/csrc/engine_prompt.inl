@@ -606,3 +606,38 @@ int engine_tta_batch(rlcf_engine* e, const float* views, int count, int N, const
     e->last_flops = flops / count;
     return RLCF_OK;
 }
+
+// ------------------------------------------------------------------ zero-shot evaluation
+// One batch of the loop TPT/zero_shot.py:139-161: model(image) of CLIPCLS_TTA (custom_clip.py:423-432, ensemble = 0) or of
+// CLIPCLS_TTA_Multiple (:555-566, the student and every further slot), the rows' top-5 and the hit counts of accuracy(), as one
+// enqueue: a tower pass per model (resampled where the model's resolution differs from in_res, :541-544), ONE ensemble-logits launch,
+// top-5, hits.  Writes zs_* and the towers' workspace only.
+int engine_zero_shot_batch(rlcf_engine* e, const float* images, int n, int in_res, int ensemble, const int64_t* target, float* logits,
+                           int32_t* top5, float* hits, hipStream_t st) {
+    if (e->C <= 0 || e->image_bank) { rlcf_set_error("rlcf_zero_shot_batch: class bank not set"); return RLCF_ERR_STATE; }
+    if (ensemble && e->n_rewards < 1) {
+        rlcf_set_error("rlcf_zero_shot_batch: ensemble asked of an engine without a further model (rlcf_engine_create_ensemble)");
+        return RLCF_ERR_STATE;
+    }
+    const int C = e->C, M = ensemble ? 1 + e->n_rewards : 1;
+    rlcf_ens_desc desc{};
+    desc.M = M;
+    for (int m = 0; m < M; ++m) {
+        ClipModel& cm = e->model[m];
+        const int D = cm.cfg.embed_dim;
+        TRY(e->zs_feat[m].ensure((size_t)e->max_views * D * sizeof(float)));
+        TRY(engine_encode_image(e, m, images, n, e->zs_feat[m].as<float>(), st, in_res));
+        desc.m[m].img = e->zs_feat[m].as<float>(); desc.m[m].ld_img = D;
+        desc.m[m].txt = m == 0 ? e->txt0.as<float>() : e->reward_cls[m - 1].as<float>(); desc.m[m].ld_txt = D;
+        desc.m[m].D = D; desc.m[m].scale = cm.logit_scale_exp;
+    }
+    float* lg = logits;
+    if (!lg) { TRY(e->zs_logits.ensure((size_t)e->max_views * C * sizeof(float))); lg = e->zs_logits.as<float>(); }
+    TRY(launch_ensemble_logits(&desc, n, C, lg, C, st));
+    int32_t* t5 = top5;
+    if (!t5) { TRY(e->zs_top5.ensure((size_t)e->max_views * 5 * sizeof(int32_t))); t5 = e->zs_top5.as<int32_t>(); }
+    if (C < 5) RLCF_HIP_CHECK(hipMemsetAsync(t5, 0xff, (size_t)n * 5 * sizeof(int32_t), st));      // top5_kernel fills min(C, 5) entries: the rest read -1
+    TRY(launch_top5_batched(lg, n, C, t5, st));
+    if (target) TRY(launch_top5_hits(t5, target, n, hits, st));
+    return RLCF_OK;
+}

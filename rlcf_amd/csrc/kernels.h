@@ -152,6 +152,8 @@ int launch_tpt_loss(const float* logits, int ld, int groups, int n, int C, float
 // mean of the n rows; w1 [H, D], b1 [H], w2 [W, H], b2 [W] (nn.Linear layout), feats [n, D] with row stride ld
 int launch_cocoop_ctx(const float* feats, int ld, int n, int mean, const float* ctx, int n_ctx, const float* w1, const float* b1,
                       const float* w2, const float* b2, int D, int H, int W, float* out, hipStream_t st);
+// ensemble cosine logits (zeroshot.hip): logits[b, c] = (1 / M) sum_m scale_m <img_m[b], txt_m[c]>, the descriptor passed by value
+int launch_ensemble_logits(const rlcf_ens_desc* desc, int n, int C, float* logits, int ld_logits, hipStream_t st);
 // recall ranks of score rows (kd.hip): gt_off = CSR offsets [rows + 1] or NULL (one ground-truth index per row)
 int launch_retrieval_ranks(const float* scores, int ld, int rows, int cols, const int32_t* gt_off, const int32_t* gt_idx, int32_t* ranks,
                            hipStream_t st);

@@ -1,6 +1,6 @@
 """Host-side mirror of the reference prompt-tuning model surface (TPT/clip/custom_clip.py):
 `PromptLearner` (:76-289), `TextEncoder` (:53-73), `ClipTestTimeTuning` (:292-344), `get_coop`
-(:347-361).  Same names, argument meaning and error behaviour; every FLOP of the towers runs in
+(:347-361), `CLIPCLS_TTA` (:364-497), `CLIPCLS_TTA_Multiple` (:500-583).  Same names, argument meaning and error behaviour; every FLOP of the towers runs in
 librlcf_hip.so (rlcf_amd.engine) — these classes hold parameters and bookkeeping only."""
 from __future__ import annotations
 
@@ -428,3 +428,99 @@ class CLIPCLS_TTA(nn.Module):
         if adapted:
             eng.set_visual_params(self._vis_init)
         return out
+
+
+class CLIPCLS_TTA_Multiple(nn.Module):
+    """TPT/clip/custom_clip.py:500-583 — the zero-shot ensemble: the mean over several CLIPs of their cosine logits.  "It is not used
+    for training in this project" (:503): no tunable state, `freeze_parameters` / `reset` / `momentum_update_model` do nothing.
+    arch[0] becomes the session's student and arch[1:] its further slots (runtime.SESSION.set_ensemble); `forward` is one
+    rlcf_zero_shot_batch call.  At most rlcf_amd._lib.ENS_MAX_MODELS models."""
+
+    def __init__(self, device, classnames, arch=["ViT-B/16", "ViT-L/14"], prompt_prefix=None, **kwargs):
+        super().__init__()
+        arch = list(arch)
+        if len(arch) > L.ENS_MAX_MODELS:
+            raise NotImplementedError(f"CLIPCLS_TTA_Multiple: {len(arch)} models; the engine mixes at most {L.ENS_MAX_MODELS} "
+                                      "(a student and RLCF_MAX_REWARDS further slots)")
+        if not arch:
+            raise ValueError("CLIPCLS_TTA_Multiple needs at least one arch")
+        self.clip_models = [clip_store.load(ar, device=device)[0] for ar in arch]
+        self.resolutions = [c.geometry.image_resolution for c in self.clip_models]                # custom_clip.py:511
+        self.n_model = len(self.clip_models)
+        self.default_resolutions = kwargs["default_resolutions"] if "default_resolutions" in kwargs.keys() else 224
+        runtime.SESSION.set_student(self.clip_models[0])
+        runtime.SESSION.set_ensemble(self.clip_models[1:])
+        self.device, self.prompt_prefix = device, prompt_prefix
+        self.classnames = [name.replace("_", " ") for name in classnames]
+        self.n_cls = len(classnames)
+        self._class_features = None
+        self._set_prompts(classnames)          # the RAW names: custom_clip.py:521 iterates `classnames`, not `self.classnames`
+
+    def _set_prompts(self, names) -> None:
+        prompts = [self.prompt_prefix + " " + name + "." for name in names]
+        self._publish(clip_store.tokenize(prompts))
+
+    def _publish(self, tokenized_prompts: torch.Tensor) -> None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.tokenized_prompts = tokenized_prompts.to(dev)
+        # as CLIPCLS_TTA: the engine's one "learnable" row is the first prompt token, looked up in the student's embedding table, so the
+        # student's cached text features are encode_text(tokenized_prompts); the further models read the tokens as they are
+        emb = self.clip_models[0].state_dict["token_embedding.weight"]
+        ctx = emb[self.tokenized_prompts[0][1:2].to(emb.device)].float()
+        runtime.SESSION.set_bank(self.tokenized_prompts, 1, ctx)
+        self._class_features = None
+
+    def _engine(self, n_images: int = 1):
+        return runtime.SESSION.engine(n_images)
+
+    @property
+    def class_features(self) -> List[torch.Tensor]:
+        """[C, D_m] per model, L2-normalised (custom_clip.py:523): what the engine cached when it took the class bank"""
+        if self._class_features is None:
+            eng = self._engine()
+            student = eng.text_features(runtime.SESSION.ctx_init.to(eng.device))
+            self._class_features = [student] + [eng.reward_class_features(m) for m in range(self.n_model - 1)]
+        return self._class_features
+
+    @torch.no_grad()
+    def get_class_features(self, tokenized_prompts):       # custom_clip.py:525-534
+        """the models' class features of `tokenized_prompts`; prompts other than the current bank are published for the call and the
+        bank is put back"""
+        current = self.tokenized_prompts
+        if tokenized_prompts.shape == current.shape and torch.equal(tokenized_prompts.to(current.device), current):
+            return list(self.class_features)
+        self._publish(tokenized_prompts)
+        out = list(self.class_features)
+        self._publish(current)
+        return out
+
+    @torch.no_grad()
+    def extract_image_features(self, images):              # custom_clip.py:536-549
+        """per model the L2-normalised image features [n, D_m] (the reference's docstring says "without normalization"; its code
+        normalises, :546); a model whose resolution differs from the images' gets the bicubic align_corners=True resample (:541-544)"""
+        eng = self._engine(images.shape[0])
+        return [eng.encode_image(w, images) for w in range(self.n_model)]
+
+    @torch.no_grad()
+    def freeze_parameters(self):
+        pass
+
+    @torch.no_grad()
+    def forward(self, image):                              # custom_clip.py:555-566
+        eng = self._engine(image.shape[0])
+        return eng.zero_shot_batch(image, ensemble=self.n_model > 1, want_top5=False)["logits"]
+
+    @torch.no_grad()
+    def reset_classnames_and_state(self, classnames, arch):    # custom_clip.py:568-575
+        self.n_cls = len(classnames)
+        classnames = [name.replace("_", " ") for name in classnames]
+        self.classnames = classnames
+        self._set_prompts(classnames)
+
+    @torch.no_grad()
+    def reset(self):
+        pass
+
+    @torch.no_grad()
+    def momentum_update_model(self):
+        pass

@@ -140,6 +140,30 @@ def l2norm_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def ensemble_logits(imgs, txts, scales, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One rlcf_ensemble_logits launch: mean over the models of scale_m * imgs[m] @ txts[m].t() (CLIPCLS_TTA_Multiple.forward,
+    custom_clip.py:555-566) -> [n, C].  imgs[m] [n, D_m] and txts[m] [C, D_m]: float32 device rows, L2-normalised by the caller, contiguous
+    within a row (any row stride that is a multiple of 4); out: optional [n, C] rows to write (row stride >= C)."""
+    imgs, txts, scales = list(imgs), list(txts), [float(s) for s in scales]
+    assert len(imgs) == len(txts) == len(scales) and len(imgs) >= 1
+    if len(imgs) > L.ENS_MAX_MODELS:
+        raise NotImplementedError(f"rlcf_ensemble_logits mixes at most {L.ENS_MAX_MODELS} models ({len(imgs)} given)")
+    n, Cn = imgs[0].shape[0], txts[0].shape[0]
+    d = L.EnsDesc()
+    d.M = len(imgs)
+    for m, (a, t, s) in enumerate(zip(imgs, txts, scales)):
+        assert a.is_cuda and t.is_cuda and a.dtype == t.dtype == torch.float32 and a.dim() == t.dim() == 2
+        assert a.stride(1) == 1 and t.stride(1) == 1 and a.shape == (n, t.shape[1]) and t.shape[0] == Cn
+        d.m[m] = L.EnsModel(a.data_ptr(), a.stride(0) if n > 1 else max(a.stride(0), a.shape[1]), t.data_ptr(),
+                            t.stride(0) if Cn > 1 else max(t.stride(0), t.shape[1]), a.shape[1], s)
+    if out is None:
+        out = torch.empty(n, Cn, device=imgs[0].device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.shape == (n, Cn) and out.stride(1) == 1
+    L.check(L.lib().rlcf_ensemble_logits(C.byref(d), n, Cn, out.data_ptr(), out.stride(0) if n > 1 else max(out.stride(0), Cn), _stream()),
+            "ensemble_logits")
+    return out
+
+
 def kd_loss_split_op(student: torch.Tensor, teacher: torch.Tensor, params: Optional[L.KdParams] = None, row_loss: bool = False):
     """One rlcf_kd_loss_split call (kd_distill_loss_v2 on few, long rows; any row stride): (loss [1], dlogits [n, C], row losses or None)."""
     assert student.dim() == 2 and student.shape == teacher.shape and student.dtype == teacher.dtype == torch.float32
@@ -351,6 +375,38 @@ class Engine:
         a = cfg.c_args(N)
         L.check(self.lib.rlcf_tta_sample_cocoop(self.h, _ptr(views), N, C.byref(a), C.byref(co), _ptr(o["image_features"]), _ptr(o["ctx_gen"]),
                                                 _stream()), "tta_sample_cocoop")
+        return o
+
+    # ---- zero-shot evaluation (TPT/zero_shot.py; CLIPCLS_TTA / CLIPCLS_TTA_Multiple forward) --------------------------------------
+    def ensemble_logits(self, imgs, txts, scales=None) -> torch.Tensor:
+        """rlcf_ensemble_logits over this engine's models (student, slot 0, ...): scales default to their exp(logit_scale)"""
+        if scales is None:
+            scales = self.logit_scales()[: len(imgs)]
+        return ensemble_logits(imgs, txts, scales)
+
+    def logit_scales(self):
+        """exp(logit_scale) of the student and every further slot, as the engine holds them (float32)"""
+        return [float(self.lib.rlcf_engine_logit_scale_exp(self.h, w)) for w in range(1 + len(self.rewards))]
+
+    def zero_shot_batch(self, images: torch.Tensor, ensemble: bool = False, target: Optional[torch.Tensor] = None,
+                        hits: Optional[torch.Tensor] = None, want_logits: bool = True, want_top5: bool = True) -> Dict[str, torch.Tensor]:
+        """One batch of TPT/zero_shot.py:139-161 (rlcf_zero_shot_batch): `images` [n, 3, R, R] are n different test images; the student
+        alone or, with ensemble, the mean over the student and every further slot.  target int64 [n] with hits float32 [2] (device,
+        ACCUMULATED: hits[0] += top-1 hits, hits[1] += top-5 hits).  -> {"logits" [n, C], "top5" [n, 5]} as asked for."""
+        images = images.to(self.device, torch.float32).contiguous()
+        n = images.shape[0]
+        o: Dict[str, torch.Tensor] = {}
+        if want_logits:
+            o["logits"] = torch.empty(n, self.n_cls, device=self.device)
+        if want_top5:
+            o["top5"] = torch.empty(n, 5, dtype=torch.int32, device=self.device)
+        if target is not None:
+            target = target.to(self.device, torch.int64).contiguous()
+            assert target.shape == (n,) and hits is not None, "one target per image, and a float32 [2] device tensor for the hit counts"
+        if hits is not None:
+            assert hits.is_cuda and hits.dtype == torch.float32 and hits.numel() == 2 and hits.is_contiguous()
+        L.check(self.lib.rlcf_zero_shot_batch(self.h, _ptr(images), n, images.shape[-1], 1 if ensemble else 0, _ptr(target), _ptr(o.get("logits")),
+                                              _ptr(o.get("top5")), _ptr(hits), _stream()), "zero_shot_batch")
         return o
 
     def ln_params(self, pristine: bool = False) -> torch.Tensor:

@@ -2,7 +2,7 @@
 lines of TPT/scripts/*.sh parse identically.  Flags the HIP path has no use for (--workers, --dataset_mode, --corruption,
 --level, --confidence_gap*) are accepted and ignored; --cocoop / --load are read by rlcf_amd.tpt_cls (TPT/tpt_cls.py:100-103); --hard_aug 1 selects the BYOL-style recipe of the view pipeline (datautils.HardAugParams);
 --kd_loss (KD / DKD / ATKD) is read by the distillation entry rlcf_amd.tune_cls_kd (TPT/tune_cls_kd.py, scripts/kd-tune.sh) and by
-nothing else."""
+nothing else; --ensemble_archs (not in the reference's parser) is read by rlcf_amd.zero_shot alone."""
 import argparse
 
 
@@ -61,5 +61,8 @@ def get_args(argv=None):
     # not in the reference's parser (default = unset -> the environment, then 1 = the reference's loop): tpt_cls_rl._loop_option
     p.add_argument("--images_per_pass", type=int, default=None, help="test images handed to the engine per call (RLCF_IMAGES_PER_PASS; 1 = the reference's loop)")
     p.add_argument("--in_flight", type=int, default=None, help="one image per engine call, this many samples side by side on their own engines / streams (RLCF_IN_FLIGHT)")
+    p.add_argument("--ensemble_archs", type=none_or_str, default=None,
+                   help="rlcf_amd.zero_shot only: comma-separated CLIP archs -> CLIPCLS_TTA_Multiple over them at --resolution, the choice TPT/zero_shot.py:50-51 "
+                        "makes by commenting a line out; unset (the default): CLIPCLS_TTA(--arch)")
     p.add_argument("--clip_root", type=str, default="", help="directory of OpenAI-layout state dicts (<arch>.pt)")
     return p.parse_args(argv)

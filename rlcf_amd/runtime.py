@@ -58,6 +58,11 @@ class Session:
     def set_rewards(self, ckpts, weights, mean: bool):
         self.rewards, self.reward_mix, self.reward_mean = list(ckpts), [float(w) for w in weights], bool(mean)
 
+    def set_ensemble(self, ckpts):
+        """further CLIPs next to the student for CLASSIFICATION (CLIPCLS_TTA_Multiple, TPT/clip/custom_clip.py:500-583): they take the
+        engine's further slots in order, as reward models do, with no reward semantics attached (no CLIPRewards object, no score mix)"""
+        self.rewards, self.reward_mix, self.reward_mean = list(ckpts), None, False
+
     def set_bank(self, tokens: torch.Tensor, n_ctx: int, ctx_init: torch.Tensor, student_tokens=None, ctx_pos=None):
         self.tokens, self.n_ctx, self.ctx_init = tokens.detach().cpu(), n_ctx, ctx_init.detach().clone()
         self.student_tokens, self.ctx_pos = student_tokens, ctx_pos       # class tokens not at the end of the prompt ('front' / 'middle')
